@@ -11,6 +11,12 @@ Launched by the driver as
 (one rank per GPU over RCCL); with no flags runs N=1 with defaults that
 finish in minutes. A "step" is one engine iteration over the whole graph;
 GTEPS counts ne edges per pull iteration (honest accounting).
+
+A plain run builds the graph, warms up, times --steps steps and prints the
+JSON result line. --dump-outputs DIR additionally writes what the last timed
+step computed (DIR/<name>.npy). --full adds the secondary measurements
+(today: the label-propagation CC algorithm next to the union-find headline
+for --app cc).
 """
 import argparse
 import json
@@ -59,6 +65,63 @@ def build_engine(args, device):
     raise ValueError(args.app)
 
 
+# --dump-outputs budget: each result array is written whole when it fits,
+# else as a fixed seeded sample of this many bytes of values (+ the sampled
+# positions as f64), so one dump stays well below 64 MB.
+DUMP_VALUE_BYTES = 16 << 20
+DUMP_SAMPLE_SEED = 20240229
+
+
+def engine_outputs(args, engine):
+    """What a caller of the timed path receives after its last step:
+    {name: device tensor}. Collective when distributed (halo PageRank
+    completes its replicated vector first)."""
+    if args.app == "pagerank":
+        engine.finalize()
+        return {"ranks": engine.ranks()}
+    if args.app == "sssp":
+        return {"labels": engine.eng.final_labels()}
+    if args.app == "cc":
+        return {"labels": engine.eng.labels}
+    return {"vectors": engine.vectors()}
+
+
+def dump_outputs(outdir, outputs):
+    """Write {name: tensor} as outdir/<name>.npy (f32 stays f32; u32
+    labels, stored bit-compatibly as int32, become exact f64; any other
+    dtype is an error). Arrays over the budget are sampled at fixed seeded
+    flat positions — one per equal-width stratum, so they are distinct and
+    ascending — also written as outdir/<name>_index.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if flat.dtype == torch.float32:
+            is_float = True
+        elif flat.dtype == torch.int32:
+            is_float = False
+        else:
+            raise TypeError(f"--dump-outputs: output {name!r} has "
+                            f"unsupported dtype {flat.dtype}")
+        itemsize = 4 if is_float else 8
+        n = flat.numel()
+        m = DUMP_VALUE_BYTES // itemsize
+        if n > m:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            stride = n // m
+            idx = np.arange(m, dtype=np.int64) * stride \
+                + rng.integers(0, stride, size=m, dtype=np.int64)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(outdir, name + "_index.npy"),
+                    idx.astype(np.float64))
+        if is_float:
+            arr = flat.cpu().numpy()
+        else:
+            arr = (flat.to(torch.int64) & 0xFFFFFFFF).cpu().numpy() \
+                .astype(np.float64)
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -89,6 +152,12 @@ def main():
     ap.add_argument("--scale", type=int, default=27)
     ap.add_argument("--edges", type=int, default=1 << 31)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (cc: the "
+                         "label-propagation algorithm)")
     args = ap.parse_args()
     apply_app_defaults(args)
 
@@ -123,15 +192,22 @@ def main():
     dx.all_reduce_max_(et)
     elapsed = float(et.item())
 
+    if args.dump_outputs:
+        outputs = engine_outputs(args, engine)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        del outputs
+        dx.barrier()
+
     edges_per_iter = args.edges
     gteps = edges_per_iter * args.steps / elapsed / 1e9
     ms_per_step = elapsed * 1000.0 / args.steps
 
     # BASELINE config 4 is named "CC (label propagation)"; the headline CC
     # engine is union-find (identical labelling, different algorithm).
-    # Always measure and report BOTH.
+    # --full measures and reports BOTH.
     labelprop = None
-    if args.app == "cc":
+    if args.full and args.app == "cc":
         del engine, part
         torch.cuda.empty_cache()
         import copy
