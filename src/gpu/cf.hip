@@ -370,10 +370,11 @@ void lux_gpu_cf_iter(uint64_t stream, uint32_t n0, const V_ID* bin0,
   CFArgs a{row_ptr, col, w, oldv, newv, row_left, K};
   if (K <= 64) {
     // LDS-tiled fast path (benchmark config K=64; reference K=20)
-    static int tile = [] {  // 32 measured best (8.6 vs 9.8 ms/sweep
-      const char* t = getenv("LUX_CF_TILE");  // NetFlix K=64: 16 wg/CU
-      return t && atoi(t) == 64 ? 64 : 32;    // beats 9 despite idle lanes)
-    }();
+    // 32 measured best (8.6 vs 9.8 ms/sweep NetFlix K=64: 16 wg/CU beats 9
+    // despite idle lanes). Read per call, like the cf_als.hip knobs, so one
+    // process can run both tiles.
+    const char* t = getenv("LUX_CF_TILE");
+    int tile = t && atoi(t) == 64 ? 64 : 32;
     if (nbig) {
       dim3 g(n2 > MAX_GRID ? MAX_GRID : n2);
       if (tile == 32)

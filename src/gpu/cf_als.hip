@@ -424,10 +424,28 @@ __device__ __forceinline__ void als_dump_gram(AlsLds* lds, f32x4 acc[10],
 // marked with a -1 sentinel, their column is zeroed, and the solve
 // takes NO step along those directions — the exact-arithmetic
 // pseudoinverse behaviour on the deficient subspace.
+//
+// The test is RELATIVE to the row's original diagonal as well as absolute:
+// an exactly deficient direction leaves pivot = lambda + rounding noise,
+// and the noise scales with the diagonal (fp32 accumulation of deg terms
+// plus 64 elimination steps, ~1e-6 * G_kk measured as a few e-3 on a
+// 40K..200K-degree hub whose sources span < K dims). Once that exceeds
+// lambda an absolute test passes pivots that are pure noise, the solve
+// divides by them, and — the hub Gram being summed with atomics — the
+// factors came out different from run to run (|item| 35 or 400 from the
+// same input, the larger ones diverging in the next sweep). Pivots below
+// ALS_PIVOT_RTOL * G_kk carry no information in fp32 and take no step.
+constexpr float ALS_PIVOT_RTOL = 1e-5f;
+
 __device__ __forceinline__ void wave_cholesky64(float* G, int lane) {
+  // lane k keeps row k's threshold; k is wave-uniform, so the loop fetches
+  // it with a readlane instead of a second LDS access per step
+  float thr = fmaxf((float)CF_LAMBDA * 0.5f,
+                    ALS_PIVOT_RTOL * G[lane * ALS_ROW + lane]);
   for (int k = 0; k < ALS_K; k++) {
     float piv = G[k * ALS_ROW + k];
-    bool ok = piv > (float)CF_LAMBDA * 0.5f;
+    bool ok = piv > __int_as_float(__builtin_amdgcn_readlane(
+                        __float_as_int(thr), k));
     float dkk = ok ? sqrtf(piv) : 1.0f;
     float lik = (lane > k && ok) ? G[lane * ALS_ROW + k] / dkk : 0.0f;
     if (lane == k) G[k * ALS_ROW + k] = ok ? dkk : -1.0f;

@@ -1,6 +1,9 @@
-"""Property-based GPU-vs-CPU equivalence on random small graphs: exercises
-bin boundaries (deg 0 / T1 / T2 edges), ragged tiles, empty frontiers and
-arbitrary sources that fixed cases miss."""
+"""Property-based GPU-vs-CPU equivalence on random small RMAT graphs:
+arbitrary sizes, seeds and sources, empty graphs and empty frontiers that
+fixed cases miss. Degrees are whatever RMAT yields, so no particular bin
+edge is hit on purpose: the exact degree-bin boundaries (31/32/33,
+2047/2048/2049, 8192/8193) are constructed in test_gpu_pull_ladder.py and
+test_gpu_cf_ladder.py."""
 import numpy as np
 import pytest
 
