@@ -190,6 +190,52 @@ def pull_finish_pr(stream, vp, newv, deg, row_left, init_rank):
                                  _u32(row_left), ctypes.c_float(init_rank))
 
 
+def pull_active_flags(stream, vp, row_ptr, flags):
+    lib().lux_gpu_pull_active_flags(_u64(stream), _u32(vp), dp(row_ptr),
+                                    dp(flags))
+
+
+def pull_active_list(stream, vp, flags, ends, active):
+    lib().lux_gpu_pull_active_list(_u64(stream), _u32(vp), dp(flags),
+                                   dp(ends), dp(active))
+
+
+def pull_build_slots(stream, n, bin_, row_ptr, row_u32, ends, cidx, rng):
+    lib().lux_gpu_pull_build_slots(_u64(stream), _u32(n), dp(bin_),
+                                   dp(row_ptr), ctypes.c_int(row_u32),
+                                   dp(ends), dp(cidx), dp(rng))
+
+
+def pull_build_hub_slots(stream, n2, bin2, row_ptr, row_u32, ends, cidx,
+                         rng):
+    lib().lux_gpu_pull_build_hub_slots(_u64(stream), _u32(n2), dp(bin2),
+                                       dp(row_ptr), ctypes.c_int(row_u32),
+                                       dp(ends), dp(cidx), dp(rng))
+
+
+def pull_slots_iter(stream, n0, cidx0, rng0, n1, cidx1, rng1, n2, cidx2,
+                    rng2, col, oldv, acc):
+    lib().lux_gpu_pull_slots_iter(_u64(stream), _u32(n0), dp(cidx0),
+                                  dp(rng0), _u32(n1), dp(cidx1), dp(rng1),
+                                  _u32(n2), dp(cidx2), dp(rng2), dp(col),
+                                  dp(oldv), dp(acc))
+
+
+def pull_finish_pr_active(stream, na, active, acc, out, deg, row_left,
+                          init_rank):
+    lib().lux_gpu_pull_finish_pr_active(_u64(stream), _u32(na), dp(active),
+                                        dp(acc), dp(out), dp(deg),
+                                        _u32(row_left),
+                                        ctypes.c_float(init_rank))
+
+
+def pull_fill_inactive_pr(stream, vp, row_ptr, out, deg, row_left,
+                          init_rank):
+    lib().lux_gpu_pull_fill_inactive_pr(_u64(stream), _u32(vp), dp(row_ptr),
+                                        dp(out), dp(deg), _u32(row_left),
+                                        ctypes.c_float(init_rank))
+
+
 def cf_als_iter(stream, n0, bin0, n1, bin1, n2, bin2, nbig, bin2v, hubidx,
                 gram_scratch, rhs_scratch, row_ptr, col, w, oldv, newv,
                 row_left, K, oldv_bf=None):

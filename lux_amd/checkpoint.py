@@ -120,3 +120,7 @@ def _refresh_slice(engine):
     if hasattr(engine, "cur_part"):
         p = engine.part
         engine.cur_part.copy_(engine.old.narrow(0, p.row_left, p.vp))
+    if hasattr(engine, "_inactive_done"):
+        # slot-path PageRank rewrites only rows with in-edges per step; the
+        # restored array may hold other values in the rest (step-0 state)
+        engine._inactive_done = False

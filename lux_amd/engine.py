@@ -79,6 +79,18 @@ def run_pull_sweeps(part, mode, oldv, newv, deg, init_rank, subset=None):
                      part.col, oldv, newv, deg, part.row_left, init_rank)
 
 
+def run_pull_slots_sweeps(part, oldv, acc):
+    """PR_SUM fold-sweeps on the slot path (GraphPart.prepare_pull_slots):
+    one launch per src window, accumulating into the active-row array
+    acc[na] — acc[i] belongs to local row part.active[i]. Same window
+    order and per-slot fold order as run_pull_sweeps."""
+    s = _stream()
+    for src in part.slot_srcs:
+        ng.pull_slots_iter(s, src["n0"], src["cidx0"], src["rng0"],
+                           src["n1"], src["cidx1"], src["rng1"], src["n2"],
+                           src["cidx2"], src["rng2"], src["col"], oldv, acc)
+
+
 def seed_pull(part, mode, oldv, newv):
     if mode == ng.PULL_PR:
         newv.zero_()
@@ -453,6 +465,60 @@ class GraphPart:
             return
         self.build_blocked(bounds)
 
+    def prepare_pull_slots(self):
+        """Slot streams + active-row list for the PageRank sweeps (built
+        once, after prepare_pull). Per bin entry of every src window (or of
+        the unblocked CSC) two coalesced streams replace the gathers from
+        the vp-wide row tables: cidx (compact index of the row in `active`,
+        the ascending list of local rows with any in-edge) and rng (the
+        entry's {begin, end} edge offsets; hub entries carry one chunk).
+        Adds keys cidx0/rng0, cidx1/rng1, cidx2/rng2 next to the bins.
+        Returns False when the slot path cannot serve this partition (an
+        unblocked CSC whose edge offsets overflow u32)."""
+        if getattr(self, "slot_srcs", None) is not None:
+            return True
+        self.prepare_pull()
+        if not self.blocks and self.ep >= (1 << 32):
+            return False
+        device, s, vp = self.device, _stream(), self.vp
+        before = torch.cuda.memory_allocated(device)
+        self.na = 0
+        self.active = torch.empty(1, dtype=U32, device=device)
+        self.slot_srcs = []
+        if vp == 0 or self.ep == 0:
+            self.slot_bytes = 0
+            return True
+        flags = torch.empty(vp, dtype=U32, device=device)
+        ng.pull_active_flags(s, vp, self.row_ptr, flags)
+        ends = torch.empty(vp, dtype=U64, device=device)  # inverse map + 1
+        partials = torch.empty(ng.scan_partials_size(vp), dtype=U64,
+                               device=device)
+        ng.scan_end_offsets(s, vp, flags, ends, partials)
+        self.na = int(ends[vp - 1].item())
+        self.active = torch.empty(max(self.na, 1), dtype=U32, device=device)
+        ng.pull_active_list(s, vp, flags, ends, self.active)
+        if self.blocks:
+            srcs = self.blocks
+        else:
+            srcs = [dict(row_ptr=self.row_ptr, row_u32=0, col=self.col,
+                         n0=self.n0, n1=self.n1, n2=self.n2, bin0=self.bin0,
+                         bin1=self.bin1, bin2=self.bin2)]
+        for src in srcs:
+            for k, build in (("0", ng.pull_build_slots),
+                             ("1", ng.pull_build_slots),
+                             ("2", ng.pull_build_hub_slots)):
+                n = src["n" + k]
+                cidx = torch.empty(max(n, 1), dtype=U32, device=device)
+                rng = torch.empty(max(2 * n, 2), dtype=U32, device=device)
+                build(s, n, src["bin" + k], src["row_ptr"],
+                      src.get("row_u32", 0), ends, cidx, rng)
+                src["cidx" + k], src["rng" + k] = cidx, rng
+            self.slot_srcs.append(src)
+        torch.cuda.synchronize()
+        del flags, ends, partials
+        self.slot_bytes = torch.cuda.memory_allocated(device) - before
+        return True
+
     def build_blocked(self, bounds):
         """Src-blocked CSC build, processed in window GROUPS sized so the
         transient (block, row) slot table (counts 4 B + cursor 8 B per
@@ -609,18 +675,35 @@ class PagerankEngine:
         degf = deg.to(F32)
         self.old = torch.where(deg == 0, torch.full_like(degf, rank0),
                                rank0 / degf.clamp(min=1.0))
-        self.new_part = torch.empty(part.vp, dtype=F32, device=device)
         self.init_rank = (1.0 - 0.15) / part.nv
+        # single rank: slot streams + active-row accumulator (the sweeps
+        # fold into acc[na], the epilogue writes `old` in place: no
+        # new_part, no slice copy). LUX_PULL_SLOTS=0 keeps the row-table
+        # kernels for A/B runs; multi-rank stays on them too.
+        import os
+        self._slots = (dx.world_size() == 1
+                       and os.environ.get("LUX_PULL_SLOTS", "1") != "0"
+                       and part.prepare_pull_slots())
+        if self._slots:
+            self.acc = torch.empty(max(part.na, 1), dtype=F32,
+                                   device=device)
+            self.new_part = None
+            # rows outside part.active hold a constant after the first
+            # step; step() writes it once (again after a checkpoint resume)
+            self._inactive_done = False
+        else:
+            self.new_part = torch.empty(part.vp, dtype=F32, device=device)
         # pipelined state: cur_part = my slice's latest values; the
         # all-gather publishing them into `old` may still be in flight
         self.cur_part = self.old.narrow(0, part.row_left,
                                         part.vp).clone()
         self._handle = None
         self.halo = _maybe_halo(part)
-        # single-GPU iteration is a fixed ~50-launch sequence (seed + 16
-        # blocked sweeps x 3 bins + epilogue + publish): captured into a
-        # hipGraph on the 2nd step and replayed (one graph launch per
-        # iteration instead of ~50 kernel launches through ctypes)
+        # single-GPU iteration is a fixed launch sequence (slot path: acc
+        # memset + one sweep launch per src window + active-row epilogue,
+        # ~18 at RMAT-27; row-table path: seed + 16 sweeps x 3 bins +
+        # epilogue + publish, ~50): captured into a hipGraph on the 2nd
+        # step and replayed (one graph launch per iteration)
         self._graph = None
         self._steps = 0
 
@@ -630,12 +713,40 @@ class PagerankEngine:
 
     def _step_body(self):
         p = self.part
+        if self._slots:
+            self.acc.zero_()
+            run_pull_slots_sweeps(p, self.old, self.acc)
+            # the kernel boundary after the last sweep makes the in-place
+            # write safe: nothing reads `old` until the next step's sweeps
+            ng.pull_finish_pr_active(_stream(), p.na, p.active, self.acc,
+                                     self.old, self.deg, p.row_left,
+                                     self.init_rank)
+            return
         run_pull(p, ng.PULL_PR, self.old, self.new_part, self.deg,
                  self.init_rank)
         self.old.narrow(0, p.row_left, p.vp).copy_(self.new_part)
 
-    def step(self):
+    def _step_single(self):
+        """Single-rank step: eager first, then captured and replayed."""
         import os
+        if self._graph is not None:
+            self._graph.replay()
+            return
+        if self._steps >= 2 and os.environ.get("LUX_HIPGRAPH", "1") \
+                == "1" and not os.environ.get("LUX_SYNC_CHECK"):
+            try:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._step_body()
+                self._graph = g
+                self._graph.replay()  # capture records, doesn't run
+                return
+            except Exception as e:  # capture unsupported: stay eager
+                print(f"[lux] hipGraph capture disabled: {e}")
+                os.environ["LUX_HIPGRAPH"] = "0"
+        self._step_body()
+
+    def step(self):
         p = self.part
         if not self._pipelined():
             if dx.world_size() > 1:  # degenerate rank (vp==0 / unblocked)
@@ -644,22 +755,14 @@ class PagerankEngine:
                 _publish_async(self, self.new_part).wait()
                 return
             self._steps += 1
-            if self._graph is not None:
-                self._graph.replay()
-                return
-            if self._steps >= 2 and os.environ.get("LUX_HIPGRAPH", "1") \
-                    == "1" and not os.environ.get("LUX_SYNC_CHECK"):
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self._step_body()
-                    self._graph = g
-                    self._graph.replay()  # capture records, doesn't run
-                    return
-                except Exception as e:  # capture unsupported: stay eager
-                    print(f"[lux] hipGraph capture disabled: {e}")
-                    os.environ["LUX_HIPGRAPH"] = "0"
-            self._step_body()
+            self._step_single()
+            if self._slots and not self._inactive_done:
+                # after the sweeps (they still read the rows' previous
+                # values), outside the captured graph
+                ng.pull_fill_inactive_pr(_stream(), p.vp, p.row_ptr,
+                                         self.old, self.deg, p.row_left,
+                                         self.init_rank)
+                self._inactive_done = True
             return
         # overlap: sweep the rank-local src block against cur_part (offset
         # base so global src ids index it) while the gather of remote

@@ -13,6 +13,11 @@
 // Bins are built once at init (degrees are static); per iteration we launch
 // prep (bin2 only) + 3 bin kernels on one stream. The same machinery runs
 // PageRank's float sum and SSSP/CC's u32 min/max dense fallback.
+//
+// PageRank additionally has a slot path (lux_gpu_pull_slots_iter): the
+// same three role bodies in ONE launch per src window, fed by per-entry
+// {compact row index, edge range} streams instead of row_ptr gathers, and
+// accumulating into an array over the rows with in-edges only.
 #include "gpu_common.h"
 
 namespace lux {
@@ -180,43 +185,98 @@ __device__ __forceinline__ typename Val<M>::T gather_range(
   return V::comb(V::comb(a0, a1), V::comb(a2, a3));
 }
 
-// ---- bin0: thread per vertex ----
-template <PullMode M, typename RowT>
-__global__ void pull_thread_kernel(uint32_t n0, const V_ID* bin0,
-                                   PullArgs a) {
+// ---- where a bin entry's output row and edge range come from ----
+// The role bodies below are written once against these small sources.
+// Table sources are the bin lists + a row_ptr table (every mode, RowT =
+// u64 plain / u32 blocked). Slot sources (PR_SUM) carry, per entry, the
+// compact output index and the edge range as two coalesced streams, so a
+// sweep never gathers from a vp-wide row table (see "slot streams" below).
+template <typename RowT>
+struct TableRows {
+  const V_ID* bin;
+  const RowT* row_ptr;
+  __device__ __forceinline__ V_ID row(uint64_t i) const { return bin[i]; }
+  __device__ __forceinline__ void range(uint64_t, V_ID v, E_ID& b,
+                                        E_ID& e) const {
+    b = row_ptr[v];
+    e = row_ptr[v + 1];
+  }
+};
+template <typename RowT>
+struct TableChunks {
+  const uint2* bin2;
+  const RowT* row_ptr;
+  __device__ __forceinline__ V_ID row(uint64_t i, uint32_t& chunk) const {
+    uint2 ent = bin2[i];
+    chunk = ent.y;
+    return ent.x;
+  }
+  __device__ __forceinline__ void range(uint64_t, V_ID v, uint32_t chunk,
+                                        E_ID& b, E_ID& e) const {
+    b = (E_ID)row_ptr[v] + (E_ID)chunk * CHUNK_EDGES;
+    e = row_ptr[v + 1];
+    if (e > b + CHUNK_EDGES) e = b + CHUNK_EDGES;
+  }
+};
+struct SlotRows {
+  const V_ID* cidx;  // compact row index (position in the active list)
+  const uint2* rng;  // {begin, end} edge offsets; hub entries: one chunk
+  __device__ __forceinline__ V_ID row(uint64_t i) const { return cidx[i]; }
+  __device__ __forceinline__ V_ID row(uint64_t i, uint32_t&) const {
+    return cidx[i];
+  }
+  __device__ __forceinline__ void range(uint64_t i, V_ID, E_ID& b,
+                                        E_ID& e) const {
+    uint2 r = rng[i];
+    b = r.x;
+    e = r.y;
+  }
+  __device__ __forceinline__ void range(uint64_t i, V_ID, uint32_t, E_ID& b,
+                                        E_ID& e) const {
+    range(i, 0, b, e);
+  }
+};
+
+// ---- bin0 role: thread per vertex (block `blk` of `nblk`) ----
+template <PullMode M, typename Src>
+__device__ __forceinline__ void pull_thread_role(uint32_t blk, uint32_t nblk,
+                                                 uint32_t n0, const Src& src,
+                                                 const PullArgs& a) {
   using V = Val<M>;
   using T = typename V::T;
   const T* oldv = (const T*)a.oldv;
   T* newv = (T*)a.newv;
-  const RowT* row_ptr = (const RowT*)a.row_ptr;
-  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n0;
+  uint64_t stride = (uint64_t)blockDim.x * nblk;
+  for (uint64_t i = blk * (uint64_t)blockDim.x + threadIdx.x; i < n0;
        i += stride) {
-    V_ID v = bin0[i];
+    V_ID v = src.row(i);
     if (V::SKIP_SETTLED && oldv[a.row_left + v] != (T)INF_LABEL)
       continue;  // settled hop label: newv keeps the seed
-    E_ID b = row_ptr[v], e = row_ptr[v + 1];
+    E_ID b, e;
+    src.range(i, v, b, e);
     T acc = gather_range<M>(oldv, a.col, b, e, 1);
     store_result<M>(&newv[v], acc);
   }
 }
 
-// ---- bin1: wave per vertex ----
-template <PullMode M, typename RowT>
-__global__ void pull_wave_kernel(uint32_t n1, const V_ID* bin1, PullArgs a) {
+// ---- bin1 role: wave per vertex ----
+template <PullMode M, typename Src>
+__device__ __forceinline__ void pull_wave_role(uint32_t blk, uint32_t nblk,
+                                               uint32_t n1, const Src& src,
+                                               const PullArgs& a) {
   using V = Val<M>;
   using T = typename V::T;
   const T* oldv = (const T*)a.oldv;
   T* newv = (T*)a.newv;
-  const RowT* row_ptr = (const RowT*)a.row_ptr;
   int lane = threadIdx.x & (WAVE - 1);
-  uint64_t wave_id = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) / WAVE;
+  uint64_t wave_id = ((uint64_t)blk * blockDim.x + threadIdx.x) / WAVE;
+  uint64_t nwaves = ((uint64_t)nblk * blockDim.x) / WAVE;
   for (uint64_t i = wave_id; i < n1; i += nwaves) {
-    V_ID v = bin1[i];
+    V_ID v = src.row(i);
     if (V::SKIP_SETTLED && oldv[a.row_left + v] != (T)INF_LABEL)
       continue;
-    E_ID b = row_ptr[v], e = row_ptr[v + 1];
+    E_ID b, e;
+    src.range(i, v, b, e);
     T acc = gather_range<M>(oldv, a.col, b + lane, e, WAVE);
     acc = V::reduce_wave(acc);
     if (lane == 0)
@@ -224,24 +284,25 @@ __global__ void pull_wave_kernel(uint32_t n1, const V_ID* bin1, PullArgs a) {
   }
 }
 
-// ---- bin2: chunk accumulation (hubs) ----
-template <PullMode M, typename RowT>
-__global__ void pull_chunk_kernel(uint32_t n2, const uint2* bin2,
-                                  PullArgs a) {
+// ---- bin2 role: chunk accumulation (hubs) ----
+// Contains __syncthreads(): every thread of a workgroup must enter it
+// together (the callers pick the role from blockIdx.x alone).
+template <PullMode M, typename Src>
+__device__ __forceinline__ void pull_chunk_role(uint32_t blk, uint32_t nblk,
+                                                uint32_t n2, const Src& src,
+                                                const PullArgs& a) {
   using V = Val<M>;
   using T = typename V::T;
   __shared__ T lds[BLOCK / WAVE];
   const T* oldv = (const T*)a.oldv;
   T* newv = (T*)a.newv;
-  const RowT* row_ptr = (const RowT*)a.row_ptr;
-  for (uint32_t i = blockIdx.x; i < n2; i += gridDim.x) {
-    uint2 ent = bin2[i];
-    V_ID v = ent.x;
+  for (uint32_t i = blk; i < n2; i += nblk) {
+    uint32_t chunk = 0;
+    V_ID v = src.row(i, chunk);
     if (V::SKIP_SETTLED && oldv[a.row_left + v] != (T)INF_LABEL)
       continue;
-    E_ID b = (E_ID)row_ptr[v] + (E_ID)ent.y * CHUNK_EDGES;
-    E_ID e = row_ptr[v + 1];
-    if (e > b + CHUNK_EDGES) e = b + CHUNK_EDGES;
+    E_ID b, e;
+    src.range(i, v, chunk, b, e);
     T acc = gather_range<M>(oldv, a.col, b + threadIdx.x, e, blockDim.x);
     // block reduce (sum mode) or wave+lds fold (min/max)
     int lane = threadIdx.x & (WAVE - 1);
@@ -256,6 +317,105 @@ __global__ void pull_chunk_kernel(uint32_t n2, const uint2* bin2,
       V::atom(&newv[v], acc);
     }
     __syncthreads();
+  }
+}
+
+template <PullMode M, typename RowT>
+__global__ void pull_thread_kernel(uint32_t n0, const V_ID* bin0,
+                                   PullArgs a) {
+  pull_thread_role<M>(blockIdx.x, gridDim.x, n0,
+                      TableRows<RowT>{bin0, (const RowT*)a.row_ptr}, a);
+}
+
+template <PullMode M, typename RowT>
+__global__ void pull_wave_kernel(uint32_t n1, const V_ID* bin1, PullArgs a) {
+  pull_wave_role<M>(blockIdx.x, gridDim.x, n1,
+                    TableRows<RowT>{bin1, (const RowT*)a.row_ptr}, a);
+}
+
+template <PullMode M, typename RowT>
+__global__ void pull_chunk_kernel(uint32_t n2, const uint2* bin2,
+                                  PullArgs a) {
+  pull_chunk_role<M>(blockIdx.x, gridDim.x, n2,
+                     TableChunks<RowT>{bin2, (const RowT*)a.row_ptr}, a);
+}
+
+// ---- slot streams: one launch per src window (PR_SUM) ----
+// a.newv is the active-row accumulator acc[na]; a.row_ptr is unused. The
+// three bins of one window touch disjoint rows, so they need no ordering:
+// each workgroup takes its role from blockIdx.x — chunk blocks first, then
+// wave, then thread, so the long-running work is dispatched first and the
+// thread-bin blocks fill the wave-bin tail.
+struct SlotBins {
+  uint32_t n0, n1, n2;  // entries per bin (n2 = hub chunks)
+  uint32_t g1, g2;      // workgroups of the wave / chunk roles
+  const V_ID *cidx0, *cidx1, *cidx2;
+  const uint2 *rng0, *rng1, *rng2;
+};
+
+template <PullMode M>
+__global__ void __launch_bounds__(BLOCK)
+    pull_slots_kernel(SlotBins s, PullArgs a) {
+  uint32_t blk = blockIdx.x;
+  if (blk < s.g2) {
+    pull_chunk_role<M>(blk, s.g2, s.n2, SlotRows{s.cidx2, s.rng2}, a);
+  } else if (blk < s.g2 + s.g1) {
+    pull_wave_role<M>(blk - s.g2, s.g1, s.n1, SlotRows{s.cidx1, s.rng1}, a);
+  } else {
+    pull_thread_role<M>(blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, s.n0,
+                        SlotRows{s.cidx0, s.rng0}, a);
+  }
+}
+
+// ---- slot / active-row builders (init time, once per graph) ----
+
+// flags[v] = 1 when local row v has any in-edge in the partition
+__global__ void pull_active_flags_kernel(V_ID vp, const E_ID* row_ptr,
+                                         uint32_t* flags) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < vp;
+       v += stride)
+    flags[v] = row_ptr[v + 1] != row_ptr[v];
+}
+
+// ends = inclusive scan of flags: an active row's compact index is
+// ends[v] - 1; scatter the ascending active list
+__global__ void pull_active_list_kernel(V_ID vp, const uint32_t* flags,
+                                        const E_ID* ends, V_ID* active) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < vp;
+       v += stride)
+    if (flags[v]) active[ends[v] - 1] = (V_ID)v;
+}
+
+template <typename RowT>
+__global__ void pull_build_slots_kernel(uint32_t n, const V_ID* bin,
+                                        const RowT* row_ptr, const E_ID* ends,
+                                        V_ID* cidx, uint2* rng) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    V_ID v = bin[i];
+    cidx[i] = (V_ID)(ends[v] - 1);
+    rng[i] = make_uint2((uint32_t)row_ptr[v], (uint32_t)row_ptr[v + 1]);
+  }
+}
+
+template <typename RowT>
+__global__ void pull_build_hub_slots_kernel(uint32_t n2, const uint2* bin2,
+                                            const RowT* row_ptr,
+                                            const E_ID* ends, V_ID* cidx,
+                                            uint2* rng) {
+  TableChunks<RowT> t{bin2, row_ptr};
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n2;
+       i += stride) {
+    uint32_t chunk;
+    V_ID v = t.row(i, chunk);
+    E_ID b, e;
+    t.range(i, v, chunk, b, e);
+    cidx[i] = (V_ID)(ends[v] - 1);
+    rng[i] = make_uint2((uint32_t)b, (uint32_t)e);
   }
 }
 
@@ -282,15 +442,48 @@ static void pull_iter(hipStream_t s, uint32_t n0, const V_ID* bin0,
 // PR epilogue over the whole partition: pr = (1-a)/nv + a*sum, stored
 // divided by out-degree (pagerank_gpu.cu:97-100, :255-259). Covers rows
 // with no in-edges too (sum stays 0 from the seed).
+__device__ __forceinline__ float finish_pr(float sum, V_ID d,
+                                           float init_rank) {
+  float pr = init_rank + PR_ALPHA * sum;
+  return d != 0 ? pr / (float)d : pr;
+}
+
 __global__ void pull_finish_pr_kernel(V_ID vp, float* newv,
                                       const V_ID* deg, V_ID row_left,
                                       float init_rank) {
   uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
   for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < vp;
+       v += stride)
+    newv[v] = finish_pr(newv[v], deg[row_left + v], init_rank);
+}
+
+// PR epilogue over the active rows only, straight into the replicated rank
+// array: out[row_left + active[i]] = finish(acc[i]). Rows outside `active`
+// keep the constant pull_fill_inactive_pr_kernel gave them.
+__global__ void pull_finish_pr_active_kernel(V_ID na, const V_ID* active,
+                                             const float* acc, float* out,
+                                             const V_ID* deg, V_ID row_left,
+                                             float init_rank) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < na;
+       i += stride) {
+    uint64_t g = (uint64_t)row_left + active[i];
+    out[g] = finish_pr(acc[i], deg[g], init_rank);
+  }
+}
+
+// Rows with no in-edge: their sum is 0 in every iteration, so the stored
+// rank is the constant finish(0). Written once, not per iteration.
+__global__ void pull_fill_inactive_pr_kernel(V_ID vp, const E_ID* row_ptr,
+                                             float* out, const V_ID* deg,
+                                             V_ID row_left,
+                                             float init_rank) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < vp;
        v += stride) {
-    float pr = init_rank + PR_ALPHA * newv[v];
-    V_ID d = deg[row_left + v];
-    newv[v] = d != 0 ? pr / (float)d : pr;
+    if (row_ptr[v + 1] != row_ptr[v]) continue;
+    uint64_t g = (uint64_t)row_left + v;
+    out[g] = finish_pr(0.0f, deg[g], init_rank);
   }
 }
 
@@ -337,6 +530,102 @@ void lux_gpu_pull_finish_pr(uint64_t stream, V_ID vp, float* newv,
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(pull_finish_pr_kernel, dim3(grid_for(vp)), dim3(BLOCK),
                      0, s, vp, newv, deg, row_left, init_rank);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ---- slot path (PR_SUM): builders, merged sweep, active-row epilogue ----
+
+void lux_gpu_pull_active_flags(uint64_t stream, V_ID vp, const E_ID* row_ptr,
+                               uint32_t* flags) {
+  hipLaunchKernelGGL(pull_active_flags_kernel, dim3(grid_for(vp)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, vp, row_ptr, flags);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ends: inclusive scan of flags (lux_gpu_scan_end_offsets); active: u32[na]
+void lux_gpu_pull_active_list(uint64_t stream, V_ID vp, const uint32_t* flags,
+                              const E_ID* ends, V_ID* active) {
+  hipLaunchKernelGGL(pull_active_list_kernel, dim3(grid_for(vp)), dim3(BLOCK),
+                     0, (hipStream_t)stream, vp, flags, ends, active);
+  LUX_POST_LAUNCH(stream);
+}
+
+// One bin list (bin0 or bin1) -> compact indices + edge ranges. Offsets
+// must fit u32 (always true for row_u32 tables; the caller checks ep for
+// u64 ones).
+void lux_gpu_pull_build_slots(uint64_t stream, uint32_t n, const V_ID* bin,
+                              const void* row_ptr, int row_u32,
+                              const E_ID* ends, V_ID* cidx, uint2* rng) {
+  if (!n) return;
+  hipStream_t s = (hipStream_t)stream;
+  if (row_u32)
+    hipLaunchKernelGGL(pull_build_slots_kernel<uint32_t>, dim3(grid_for(n)),
+                       dim3(BLOCK), 0, s, n, bin, (const uint32_t*)row_ptr,
+                       ends, cidx, rng);
+  else
+    hipLaunchKernelGGL(pull_build_slots_kernel<uint64_t>, dim3(grid_for(n)),
+                       dim3(BLOCK), 0, s, n, bin, (const uint64_t*)row_ptr,
+                       ends, cidx, rng);
+  LUX_POST_LAUNCH(stream);
+}
+
+// bin2 (row, chunk) entries -> compact index + that chunk's edge range
+void lux_gpu_pull_build_hub_slots(uint64_t stream, uint32_t n2,
+                                  const uint2* bin2, const void* row_ptr,
+                                  int row_u32, const E_ID* ends, V_ID* cidx,
+                                  uint2* rng) {
+  if (!n2) return;
+  hipStream_t s = (hipStream_t)stream;
+  if (row_u32)
+    hipLaunchKernelGGL(pull_build_hub_slots_kernel<uint32_t>,
+                       dim3(grid_for(n2)), dim3(BLOCK), 0, s, n2, bin2,
+                       (const uint32_t*)row_ptr, ends, cidx, rng);
+  else
+    hipLaunchKernelGGL(pull_build_hub_slots_kernel<uint64_t>,
+                       dim3(grid_for(n2)), dim3(BLOCK), 0, s, n2, bin2,
+                       (const uint64_t*)row_ptr, ends, cidx, rng);
+  LUX_POST_LAUNCH(stream);
+}
+
+// One PR_SUM sweep of one src window (or the unblocked CSC) in ONE launch:
+// acc[cidx] = acc[cidx] + sum over the slot's edges of oldv[col[j]].
+void lux_gpu_pull_slots_iter(uint64_t stream, uint32_t n0, const V_ID* cidx0,
+                             const uint2* rng0, uint32_t n1,
+                             const V_ID* cidx1, const uint2* rng1,
+                             uint32_t n2, const V_ID* cidx2,
+                             const uint2* rng2, const V_ID* col,
+                             const float* oldv, float* acc) {
+  // per-role grids: what the three separate launches use
+  uint32_t g2 = n2 ? (n2 > (uint32_t)MAX_GRID ? MAX_GRID : n2) : 0;
+  uint32_t g1 = n1 ? grid_for((uint64_t)n1 * WAVE) : 0;
+  uint32_t g0 = n0 ? grid_for(n0) : 0;
+  if (g0 + g1 + g2 == 0) return;
+  SlotBins sb{n0, n1, n2, g1, g2, cidx0, cidx1, cidx2, rng0, rng1, rng2};
+  PullArgs a{nullptr, col, oldv, acc, nullptr, 0, 0.0f};
+  hipLaunchKernelGGL(pull_slots_kernel<PR_SUM>, dim3(g0 + g1 + g2),
+                     dim3(BLOCK), 0, (hipStream_t)stream, sb, a);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_pull_finish_pr_active(uint64_t stream, V_ID na,
+                                   const V_ID* active, const float* acc,
+                                   float* out, const V_ID* deg, V_ID row_left,
+                                   float init_rank) {
+  if (!na) return;
+  hipLaunchKernelGGL(pull_finish_pr_active_kernel, dim3(grid_for(na)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, na, active, acc,
+                     out, deg, row_left, init_rank);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_pull_fill_inactive_pr(uint64_t stream, V_ID vp,
+                                   const E_ID* row_ptr, float* out,
+                                   const V_ID* deg, V_ID row_left,
+                                   float init_rank) {
+  if (!vp) return;
+  hipLaunchKernelGGL(pull_fill_inactive_pr_kernel, dim3(grid_for(vp)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, vp, row_ptr, out,
+                     deg, row_left, init_rank);
   LUX_POST_LAUNCH(stream);
 }
 

@@ -85,6 +85,37 @@ void lux_gpu_pull_iter(uint64_t stream, int mode, uint32_t n0,
 void lux_gpu_pull_finish_pr(uint64_t stream, lux::V_ID vp, float* newv,
                             const lux::V_ID* deg, lux::V_ID row_left,
                             float init_rank);
+// slot path (PR_SUM): per-entry {compact row index, edge range} streams
+// next to the bins, an accumulator over the rows with in-edges only, one
+// launch per src window, epilogue straight into the replicated array
+void lux_gpu_pull_active_flags(uint64_t stream, lux::V_ID vp,
+                               const lux::E_ID* row_ptr, uint32_t* flags);
+void lux_gpu_pull_active_list(uint64_t stream, lux::V_ID vp,
+                              const uint32_t* flags, const lux::E_ID* ends,
+                              lux::V_ID* active);
+void lux_gpu_pull_build_slots(uint64_t stream, uint32_t n,
+                              const lux::V_ID* bin, const void* row_ptr,
+                              int row_u32, const lux::E_ID* ends,
+                              lux::V_ID* cidx, lux_uint2* rng);
+void lux_gpu_pull_build_hub_slots(uint64_t stream, uint32_t n2,
+                                  const lux_uint2* bin2, const void* row_ptr,
+                                  int row_u32, const lux::E_ID* ends,
+                                  lux::V_ID* cidx, lux_uint2* rng);
+void lux_gpu_pull_slots_iter(uint64_t stream, uint32_t n0,
+                             const lux::V_ID* cidx0, const lux_uint2* rng0,
+                             uint32_t n1, const lux::V_ID* cidx1,
+                             const lux_uint2* rng1, uint32_t n2,
+                             const lux::V_ID* cidx2, const lux_uint2* rng2,
+                             const lux::V_ID* col, const float* oldv,
+                             float* acc);
+void lux_gpu_pull_finish_pr_active(uint64_t stream, lux::V_ID na,
+                                   const lux::V_ID* active, const float* acc,
+                                   float* out, const lux::V_ID* deg,
+                                   lux::V_ID row_left, float init_rank);
+void lux_gpu_pull_fill_inactive_pr(uint64_t stream, lux::V_ID vp,
+                                   const lux::E_ID* row_ptr, float* out,
+                                   const lux::V_ID* deg, lux::V_ID row_left,
+                                   float init_rank);
 
 // push.hip
 void lux_gpu_csr_scatter(uint64_t stream, uint64_t ep, const lux::V_ID* col,
