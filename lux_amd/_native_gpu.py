@@ -221,6 +221,33 @@ def pull_slots_iter(stream, n0, cidx0, rng0, n1, cidx1, rng1, n2, cidx2,
                                   dp(oldv), dp(acc))
 
 
+def pull_slot_counts(stream, n, rng, cnt):
+    lib().lux_gpu_pull_slot_counts(_u64(stream), _u32(n), dp(rng), dp(cnt))
+
+
+def pull_stream_copy(stream, n0, rng0, off0, col, scol0):
+    lib().lux_gpu_pull_stream_copy(_u64(stream), _u32(n0), dp(rng0),
+                                   dp(off0), dp(col), dp(scol0))
+
+
+def pull_stream_tile_counts(stream, n0, off0, cnt):
+    lib().lux_gpu_pull_stream_tile_counts(_u64(stream), _u32(n0), dp(off0),
+                                          dp(cnt))
+
+
+def pull_stream_tile_fill(stream, n0, off0, ends, tile0):
+    lib().lux_gpu_pull_stream_tile_fill(_u64(stream), _u32(n0), dp(off0),
+                                        dp(ends), dp(tile0))
+
+
+def pull_slots_stream_iter(stream, n0, cidx0, nt, tile0, off0, scol0, n1,
+                           cidx1, rng1, n2, cidx2, rng2, col, oldv, acc):
+    lib().lux_gpu_pull_slots_stream_iter(
+        _u64(stream), _u32(n0), dp(cidx0), _u32(nt), dp(tile0), dp(off0),
+        dp(scol0), _u32(n1), dp(cidx1), dp(rng1), _u32(n2), dp(cidx2),
+        dp(rng2), dp(col), dp(oldv), dp(acc))
+
+
 def pull_finish_pr_active(stream, na, active, acc, out, deg, row_left,
                           init_rank):
     lib().lux_gpu_pull_finish_pr_active(_u64(stream), _u32(na), dp(active),

@@ -27,6 +27,8 @@ LLC_BLOCK_SHIFT = 23  # 2^23 verts * 4 B = 32 MB gather window: measured
 # the 256 MB LLC also carries the col stream and newv partials; below 32 MB
 # the per-sweep row overhead wins)
 
+PULL_STREAM_DEFAULT = "1"  # LUX_PULL_STREAM when unset (BENCHLOG r4.1)
+
 
 def _bins_for(row_ptr, vp, ep, device, compact=False):
     """Run the bin-build kernel over one row_ptr; returns counts + lists."""
@@ -79,12 +81,33 @@ def run_pull_sweeps(part, mode, oldv, newv, deg, init_rank, subset=None):
                      part.col, oldv, newv, deg, part.row_left, init_rank)
 
 
-def run_pull_slots_sweeps(part, oldv, acc):
+def pull_stream_enabled():
+    """LUX_PULL_STREAM: run the thread bin of the slot sweeps as the stream
+    role (one wave per tile of consecutive slots, lane = edge) instead of
+    one thread per slot. Same sums bit for bit; =0 / =1 for A/B runs."""
+    import os
+    return os.environ.get("LUX_PULL_STREAM", PULL_STREAM_DEFAULT) != "0"
+
+
+def run_pull_slots_sweeps(part, oldv, acc, stream=None):
     """PR_SUM fold-sweeps on the slot path (GraphPart.prepare_pull_slots):
     one launch per src window, accumulating into the active-row array
     acc[na] — acc[i] belongs to local row part.active[i]. Same window
-    order and per-slot fold order as run_pull_sweeps."""
+    order and per-slot fold order as run_pull_sweeps. stream: thread bin
+    by the stream role (GraphPart.prepare_pull_stream; None = what
+    LUX_PULL_STREAM says)."""
     s = _stream()
+    if stream is None:
+        stream = pull_stream_enabled()
+    if stream:
+        part.prepare_pull_stream()  # no-op once built (engines: at init)
+        for src in part.slot_srcs:
+            ng.pull_slots_stream_iter(
+                s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
+                src["off0"], src["scol0"], src["n1"], src["cidx1"],
+                src["rng1"], src["n2"], src["cidx2"], src["rng2"],
+                src["col"], oldv, acc)
+        return
     for src in part.slot_srcs:
         ng.pull_slots_iter(s, src["n0"], src["cidx0"], src["rng0"],
                            src["n1"], src["cidx1"], src["rng1"], src["n2"],
@@ -519,6 +542,49 @@ class GraphPart:
         self.slot_bytes = torch.cuda.memory_allocated(device) - before
         return True
 
+    def prepare_pull_stream(self):
+        """Stream-role tables for the thread bin of every slot source (built
+        once, after prepare_pull_slots). off0: u32[n0+1] exclusive scan of
+        the bin's per-slot edge counts; scol0: the bin's col entries copied
+        into that order (contiguous, unlike in col where wave-bin and hub
+        rows sit in between); tile0: u32[nt+1] first slot of each tile — a
+        run of consecutive slots with at most 64 slots and 512 edges, cut
+        greedily inside fixed 64-slot groups. Their bytes are added to
+        slot_bytes (and kept apart in stream_bytes)."""
+        if getattr(self, "stream_bytes", None) is not None:
+            return
+        device, s = self.device, _stream()
+        before = torch.cuda.memory_allocated(device)
+        for src in self.slot_srcs:
+            n0 = src["n0"]
+            if not n0:
+                src["nt"] = 0
+                src["off0"] = src["scol0"] = src["tile0"] = None
+                continue
+            cnt = torch.empty(n0, dtype=U32, device=device)
+            ng.pull_slot_counts(s, n0, src["rng0"], cnt)
+            ends = torch.empty(n0, dtype=U64, device=device)
+            partials = torch.empty(ng.scan_partials_size(n0), dtype=U64,
+                                   device=device)
+            ng.scan_end_offsets(s, n0, cnt, ends, partials)
+            off0 = torch.zeros(n0 + 1, dtype=U32, device=device)
+            ng.u64_to_u32(s, n0, ends, off0.narrow(0, 1, n0))
+            scol0 = torch.empty(int(ends[n0 - 1].item()), dtype=U32,
+                                device=device)
+            ng.pull_stream_copy(s, n0, src["rng0"], off0, src["col"], scol0)
+            ngroups = (n0 + 63) // 64
+            ng.pull_stream_tile_counts(s, n0, off0, cnt)  # cnt: reused
+            ng.scan_end_offsets(s, ngroups, cnt, ends, partials)
+            nt = int(ends[ngroups - 1].item())
+            tile0 = torch.empty(nt + 1, dtype=U32, device=device)
+            ng.pull_stream_tile_fill(s, n0, off0, ends, tile0)
+            src["nt"], src["off0"], src["scol0"], src["tile0"] = \
+                nt, off0, scol0, tile0
+        torch.cuda.synchronize()
+        cnt = ends = partials = None
+        self.stream_bytes = torch.cuda.memory_allocated(device) - before
+        self.slot_bytes += self.stream_bytes
+
     def build_blocked(self, bounds):
         """Src-blocked CSC build, processed in window GROUPS sized so the
         transient (block, row) slot table (counts 4 B + cursor 8 B per
@@ -684,6 +750,11 @@ class PagerankEngine:
         self._slots = (dx.world_size() == 1
                        and os.environ.get("LUX_PULL_SLOTS", "1") != "0"
                        and part.prepare_pull_slots())
+        # LUX_PULL_STREAM=0 keeps the thread-per-slot role for the thread
+        # bin of the slot sweeps (A/B runs); default: the stream role
+        self._stream_role = bool(self._slots) and pull_stream_enabled()
+        if self._stream_role:
+            part.prepare_pull_stream()
         if self._slots:
             self.acc = torch.empty(max(part.na, 1), dtype=F32,
                                    device=device)
@@ -715,7 +786,8 @@ class PagerankEngine:
         p = self.part
         if self._slots:
             self.acc.zero_()
-            run_pull_slots_sweeps(p, self.old, self.acc)
+            run_pull_slots_sweeps(p, self.old, self.acc,
+                                  stream=self._stream_role)
             # the kernel boundary after the last sweep makes the in-place
             # write safe: nothing reads `old` until the next step's sweeps
             ng.pull_finish_pr_active(_stream(), p.na, p.active, self.acc,

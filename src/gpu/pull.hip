@@ -17,7 +17,9 @@
 // PageRank additionally has a slot path (lux_gpu_pull_slots_iter): the
 // same three role bodies in ONE launch per src window, fed by per-entry
 // {compact row index, edge range} streams instead of row_ptr gathers, and
-// accumulating into an array over the rows with in-edges only.
+// accumulating into an array over the rows with in-edges only. Its thread
+// bin can run as the stream role instead (lux_gpu_pull_slots_stream_iter):
+// one wave per tile of consecutive slots, lane = edge, row sums out of LDS.
 #include "gpu_common.h"
 
 namespace lux {
@@ -367,6 +369,128 @@ __global__ void __launch_bounds__(BLOCK)
   }
 }
 
+// ---- stream role: the thread bin as one contiguous edge stream ----
+// A thread-bin slot holds 3-4 edges on average, so thread-per-slot runs the
+// rolled tail of gather_range: one dependent col -> oldv chain per lane, a
+// fifth of the lanes active. Here one wave takes a TILE of consecutive
+// thread-bin slots (at most 64 slots and TILE_EDGES edges), reads the tile's
+// col entries from scol0 (the bin's edges copied contiguously in slot order)
+// with lane = edge, gathers oldv for them as independent loads into the
+// wave's LDS segment, and lane r then folds slot r's segment out of LDS in
+// gather_range's step-1 association order (bit-identical sums).
+constexpr uint32_t TILE_EDGES = 512;
+constexpr uint32_t TILE_GROUP = WAVE;  // tiles never span a 64-slot group
+
+struct SlotStream {
+  uint32_t nt;            // tiles
+  const uint32_t* tile0;  // u32[nt+1]: first slot of each tile, [nt] = n0
+  const uint32_t* off0;   // u32[n0+1]: exclusive scan of the slots' degrees
+  const V_ID* scol0;      // u32[off0[n0]]
+};
+
+// gather_range<PR_SUM>(.., step 1) over values already sitting in LDS
+__device__ __forceinline__ float lds_range_sum(const float* v, uint32_t j,
+                                               uint32_t e) {
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+  for (; j + 3 < e; j += 4) {
+    a0 = a0 + v[j];
+    a1 = a1 + v[j + 1];
+    a2 = a2 + v[j + 2];
+    a3 = a3 + v[j + 3];
+  }
+  for (; j < e; j++) a0 = a0 + v[j];
+  return (a0 + a1) + (a2 + a3);
+}
+
+// Wave-local throughout (no __syncthreads()): a wave's LDS accesses issue
+// in order, the wavefront fence only keeps the compiler from moving them.
+template <PullMode M>
+__device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
+                                                 const SlotStream& st,
+                                                 const V_ID* cidx0,
+                                                 const PullArgs& a) {
+  static_assert(M == PR_SUM, "stream role: float sums only");
+  constexpr uint32_t NW = BLOCK / WAVE;
+  __shared__ float vals[NW][TILE_EDGES];
+  const float* oldv = (const float*)a.oldv;
+  float* acc = (float*)a.newv;
+  uint32_t lane = threadIdx.x & (WAVE - 1);
+  uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float* v = vals[wid];
+  uint64_t nwaves = (uint64_t)nblk * NW;
+  uint64_t t = (uint64_t)blk * NW + wid;
+  if (t >= st.nt) return;
+  uint32_t s0 = st.tile0[t], s1 = st.tile0[t + 1];
+  uint32_t e0 = st.off0[s0], e1 = st.off0[s1];
+  for (;;) {
+    // the next tile's bounds are fetched under this tile's gathers
+    uint64_t tn = t + nwaves;
+    bool more = tn < st.nt;
+    uint32_t s0n = 0, s1n = 0, e0n = 0, e1n = 0;
+    if (more) {
+      s0n = st.tile0[tn];
+      s1n = st.tile0[tn + 1];
+    }
+    uint32_t rb = 0, re = 0;
+    V_ID ci = 0;
+    float prev = 0.0f;
+    bool row = lane < s1 - s0;
+    if (row) {
+      rb = st.off0[s0 + lane] - e0;
+      re = st.off0[s0 + lane + 1] - e0;
+      ci = cidx0[s0 + lane];
+      prev = acc[ci];  // one writer per row and sweep
+    }
+    // at most TILE_EDGES / (4 * WAVE) = 2 trips; 4 col loads, then 4
+    // independent gathers per lane
+    for (uint32_t base = e0 + lane; base < e1; base += 4 * WAVE) {
+      uint32_t i0 = base, i1 = base + WAVE, i2 = base + 2 * WAVE,
+               i3 = base + 3 * WAVE;
+      bool p1 = i1 < e1, p2 = i2 < e1, p3 = i3 < e1;
+      V_ID c0 = st.scol0[i0];
+      V_ID c1 = p1 ? st.scol0[i1] : 0;
+      V_ID c2 = p2 ? st.scol0[i2] : 0;
+      V_ID c3 = p3 ? st.scol0[i3] : 0;
+      float x0 = oldv[c0];
+      float x1 = p1 ? oldv[c1] : 0.0f;
+      float x2 = p2 ? oldv[c2] : 0.0f;
+      float x3 = p3 ? oldv[c3] : 0.0f;
+      v[i0 - e0] = x0;
+      if (p1) v[i1 - e0] = x1;
+      if (p2) v[i2 - e0] = x2;
+      if (p3) v[i3 - e0] = x3;
+    }
+    if (more) {
+      e0n = st.off0[s0n];
+      e1n = st.off0[s1n];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (row) acc[ci] = Val<M>::comb(lds_range_sum(v, rb, re), prev);
+    // the next tile's LDS writes stay behind these reads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (!more) break;
+    t = tn;
+    s0 = s0n, s1 = s1n, e0 = e0n, e1 = e1n;
+  }
+}
+
+template <PullMode M>
+__global__ void __launch_bounds__(BLOCK)
+    pull_slots_stream_kernel(SlotBins s, SlotStream st, PullArgs a) {
+  uint32_t blk = blockIdx.x;
+  if (blk < s.g2) {
+    pull_chunk_role<M>(blk, s.g2, s.n2, SlotRows{s.cidx2, s.rng2}, a);
+  } else if (blk < s.g2 + s.g1) {
+    pull_wave_role<M>(blk - s.g2, s.g1, s.n1, SlotRows{s.cidx1, s.rng1}, a);
+  } else {
+    pull_stream_role<M>(blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, st,
+                        s.cidx0, a);
+  }
+}
+
 // ---- slot / active-row builders (init time, once per graph) ----
 
 // flags[v] = 1 when local row v has any in-edge in the partition
@@ -419,6 +543,76 @@ __global__ void pull_build_hub_slots_kernel(uint32_t n2, const uint2* bin2,
   }
 }
 
+// ---- stream-role builders (thread bin of one window) ----
+
+// cnt[i] = edges of slot i; its scan is off0
+__global__ void pull_slot_counts_kernel(uint32_t n, const uint2* rng,
+                                        uint32_t* cnt) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    uint2 r = rng[i];
+    cnt[i] = r.y - r.x;
+  }
+}
+
+// scol0[off0[i] + j] = col[rng0[i].x + j]: the thread bin's edges made
+// contiguous in slot order (wave-bin and hub rows sit between them in col)
+__global__ void pull_stream_copy_kernel(uint32_t n0, const uint2* rng0,
+                                        const uint32_t* off0,
+                                        const V_ID* col, V_ID* scol0) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n0;
+       i += stride) {
+    uint2 r = rng0[i];
+    uint32_t o = off0[i];
+    for (uint32_t j = r.x; j < r.y; j++) scol0[o + (j - r.x)] = col[j];
+  }
+}
+
+// Greedy cut of the 64-slot group g into tiles of at most TILE_EDGES edges;
+// returns the tile count and, with `out`, writes each tile's first slot.
+// One slot is below T1 <= TILE_EDGES edges, so every cut makes progress.
+__device__ __forceinline__ uint32_t cut_tile_group(uint64_t g, uint32_t n0,
+                                                   const uint32_t* off0,
+                                                   uint32_t* out) {
+  uint64_t s = g * TILE_GROUP;
+  uint64_t send = s + TILE_GROUP < n0 ? s + TILE_GROUP : n0;
+  uint32_t begin = off0[s], nt = 1;
+  if (out) out[0] = (uint32_t)s;
+  for (uint64_t i = s; i < send; i++) {
+    if (off0[i + 1] - begin > TILE_EDGES) {  // slot i opens the next tile
+      begin = off0[i];
+      if (out) out[nt] = (uint32_t)i;
+      nt++;
+    }
+  }
+  return nt;
+}
+
+__global__ void pull_stream_tile_counts_kernel(uint32_t n0,
+                                               const uint32_t* off0,
+                                               uint32_t* cnt) {
+  uint64_t ngroups = ((uint64_t)n0 + TILE_GROUP - 1) / TILE_GROUP;
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+       g < ngroups; g += stride)
+    cnt[g] = cut_tile_group(g, n0, off0, nullptr);
+}
+
+// ends = inclusive scan of the per-group tile counts
+__global__ void pull_stream_tile_fill_kernel(uint32_t n0,
+                                             const uint32_t* off0,
+                                             const E_ID* ends,
+                                             uint32_t* tile0) {
+  uint64_t ngroups = ((uint64_t)n0 + TILE_GROUP - 1) / TILE_GROUP;
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+       g < ngroups; g += stride) {
+    cut_tile_group(g, n0, off0, tile0 + (g ? ends[g - 1] : 0));
+    if (g == ngroups - 1) tile0[ends[g]] = n0;
+  }
+}
 
 template <PullMode M, typename RowT>
 static void pull_iter(hipStream_t s, uint32_t n0, const V_ID* bin0,
@@ -604,6 +798,69 @@ void lux_gpu_pull_slots_iter(uint64_t stream, uint32_t n0, const V_ID* cidx0,
   PullArgs a{nullptr, col, oldv, acc, nullptr, 0, 0.0f};
   hipLaunchKernelGGL(pull_slots_kernel<PR_SUM>, dim3(g0 + g1 + g2),
                      dim3(BLOCK), 0, (hipStream_t)stream, sb, a);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ---- stream role: builders and the sweep that runs it ----
+
+// cnt[i] = rng[i].y - rng[i].x (u32[n]); scanned by the caller into off0
+void lux_gpu_pull_slot_counts(uint64_t stream, uint32_t n, const uint2* rng,
+                              uint32_t* cnt) {
+  if (!n) return;
+  hipLaunchKernelGGL(pull_slot_counts_kernel, dim3(grid_for(n)), dim3(BLOCK),
+                     0, (hipStream_t)stream, n, rng, cnt);
+  LUX_POST_LAUNCH(stream);
+}
+
+// off0: u32[n0+1] exclusive scan of the counts; scol0: u32[off0[n0]]
+void lux_gpu_pull_stream_copy(uint64_t stream, uint32_t n0, const uint2* rng0,
+                              const uint32_t* off0, const V_ID* col,
+                              V_ID* scol0) {
+  if (!n0) return;
+  hipLaunchKernelGGL(pull_stream_copy_kernel, dim3(grid_for(n0)), dim3(BLOCK),
+                     0, (hipStream_t)stream, n0, rng0, off0, col, scol0);
+  LUX_POST_LAUNCH(stream);
+}
+
+// cnt: u32[ceil(n0 / 64)] tiles per 64-slot group
+void lux_gpu_pull_stream_tile_counts(uint64_t stream, uint32_t n0,
+                                     const uint32_t* off0, uint32_t* cnt) {
+  if (!n0) return;
+  uint64_t ngroups = ((uint64_t)n0 + TILE_GROUP - 1) / TILE_GROUP;
+  hipLaunchKernelGGL(pull_stream_tile_counts_kernel, dim3(grid_for(ngroups)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, n0, off0, cnt);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ends: inclusive scan of cnt (nt = its last entry); tile0: u32[nt+1]
+void lux_gpu_pull_stream_tile_fill(uint64_t stream, uint32_t n0,
+                                   const uint32_t* off0, const E_ID* ends,
+                                   uint32_t* tile0) {
+  if (!n0) return;
+  uint64_t ngroups = ((uint64_t)n0 + TILE_GROUP - 1) / TILE_GROUP;
+  hipLaunchKernelGGL(pull_stream_tile_fill_kernel, dim3(grid_for(ngroups)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, n0, off0, ends,
+                     tile0);
+  LUX_POST_LAUNCH(stream);
+}
+
+// lux_gpu_pull_slots_iter with the thread bin run by the stream role: one
+// wave per tile instead of one thread per slot. Same sums, bit for bit.
+void lux_gpu_pull_slots_stream_iter(
+    uint64_t stream, uint32_t n0, const V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const V_ID* scol0,
+    uint32_t n1, const V_ID* cidx1, const uint2* rng1, uint32_t n2,
+    const V_ID* cidx2, const uint2* rng2, const V_ID* col, const float* oldv,
+    float* acc) {
+  uint32_t g2 = n2 ? (n2 > (uint32_t)MAX_GRID ? MAX_GRID : n2) : 0;
+  uint32_t g1 = n1 ? grid_for((uint64_t)n1 * WAVE) : 0;
+  uint32_t g0 = n0 && nt ? grid_for((uint64_t)nt * WAVE) : 0;
+  if (g0 + g1 + g2 == 0) return;
+  SlotBins sb{n0, n1, n2, g1, g2, cidx0, cidx1, cidx2, nullptr, rng1, rng2};
+  SlotStream st{g0 ? nt : 0, tile0, off0, scol0};
+  PullArgs a{nullptr, col, oldv, acc, nullptr, 0, 0.0f};
+  hipLaunchKernelGGL(pull_slots_stream_kernel<PR_SUM>, dim3(g0 + g1 + g2),
+                     dim3(BLOCK), 0, (hipStream_t)stream, sb, st, a);
   LUX_POST_LAUNCH(stream);
 }
 

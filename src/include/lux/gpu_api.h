@@ -108,6 +108,23 @@ void lux_gpu_pull_slots_iter(uint64_t stream, uint32_t n0,
                              const lux::V_ID* cidx2, const lux_uint2* rng2,
                              const lux::V_ID* col, const float* oldv,
                              float* acc);
+// stream role (thread bin as a contiguous edge stream, one wave per tile)
+void lux_gpu_pull_slot_counts(uint64_t stream, uint32_t n,
+                              const lux_uint2* rng, uint32_t* cnt);
+void lux_gpu_pull_stream_copy(uint64_t stream, uint32_t n0,
+                              const lux_uint2* rng0, const uint32_t* off0,
+                              const lux::V_ID* col, lux::V_ID* scol0);
+void lux_gpu_pull_stream_tile_counts(uint64_t stream, uint32_t n0,
+                                     const uint32_t* off0, uint32_t* cnt);
+void lux_gpu_pull_stream_tile_fill(uint64_t stream, uint32_t n0,
+                                   const uint32_t* off0,
+                                   const lux::E_ID* ends, uint32_t* tile0);
+void lux_gpu_pull_slots_stream_iter(
+    uint64_t stream, uint32_t n0, const lux::V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const lux::V_ID* scol0,
+    uint32_t n1, const lux::V_ID* cidx1, const lux_uint2* rng1, uint32_t n2,
+    const lux::V_ID* cidx2, const lux_uint2* rng2, const lux::V_ID* col,
+    const float* oldv, float* acc);
 void lux_gpu_pull_finish_pr_active(uint64_t stream, lux::V_ID na,
                                    const lux::V_ID* active, const float* acc,
                                    float* out, const lux::V_ID* deg,
