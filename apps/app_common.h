@@ -33,6 +33,8 @@ struct AppArgs {
   lux::V_ID users = 0;         // col_filter -als: bipartite user/item
                                // boundary for Gauss-Seidel alternation
                                // (auto-set from -synthetic bipartite:...)
+  bool weighted = false;       // sssp: min-plus over edge weights — Python
+                               // engine only; the native driver refuses
 };
 
 inline AppArgs parse_input_args(int argc, char** argv) {
@@ -52,6 +54,8 @@ inline AppArgs parse_input_args(int argc, char** argv) {
     else if (f == "-als") a.als = true;
     else if (f == "-users") a.users = (lux::V_ID)atoll(next());
     else if (f == "-labelprop") a.labelprop = true;
+    else if (f == "-weighted") a.weighted = true;
+    else if (f == "-wmax") next();  // value of the Python driver's flag
     else if (f.rfind("-ll:", 0) == 0 || f.rfind("-lg:", 0) == 0) {
       if (i + 1 < argc && argv[i + 1][0] != '-') i++;  // value-flag: skip
     } else {

@@ -11,6 +11,15 @@ using namespace lux;
 
 int main(int argc, char** argv) {
   AppArgs a = parse_input_args(argc, argv);
+  if (a.weighted) {
+    // the native runtime relaxes hops only; printing hop distances for a
+    // -weighted run would be silently wrong
+    fprintf(stderr,
+            "sssp: -weighted is not supported by the native runtime (it "
+            "computes hop distances only); run `python -m lux_amd.apps.sssp "
+            "-weighted ...` for weighted shortest paths\n");
+    return 2;
+  }
   if (const char* mr = getenv("LUX_MULTI_RANK")) {
     // re-exec'd native multi-GPU push worker (meta-record exchange)
     HostCSC g;

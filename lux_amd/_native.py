@@ -58,6 +58,8 @@ if cpu is not None:
     cpu.lux_cc_iter_part.restype = ctypes.c_uint32
     cpu.lux_sssp_cpu.restype = ctypes.c_int
     cpu.lux_cc_cpu.restype = ctypes.c_int
+    cpu.lux_sssp_weighted_cpu.restype = ctypes.c_int
+    cpu.lux_sssp_weighted_check.restype = ctypes.c_uint64
 
 
 # ---------------- CPU wrappers ----------------
@@ -248,6 +250,34 @@ def cc_check(nv, ne, col_end, src, label):
     return cpu.lux_cc_check(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
                             ptr(col_end, u64p), ptr(src, u32p),
                             ptr(label, u32p))
+
+
+def hash_weights(nv, col_end, src, wmax, seed=1):
+    """weight[i] = edge_hash_weight(seed, src[i], dst(i), wmax), in [1, wmax]
+    (src/include/lux/rmat.h)."""
+    weight = np.empty(len(src), np.int32)
+    cpu.lux_hash_weights(ctypes.c_uint32(nv), ptr(col_end, u64p),
+                         ptr(src, u32p), ctypes.c_uint64(seed),
+                         ctypes.c_uint32(wmax), ptr(weight, i32p))
+    return weight
+
+
+def sssp_weighted_cpu(nv, ne, col_end, src, weight, source):
+    label = np.empty(nv, np.uint32)
+    r = cpu.lux_sssp_weighted_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                                  ptr(col_end, u64p), ptr(src, u32p),
+                                  ptr(weight, i32p), ctypes.c_uint32(source),
+                                  ptr(label, u32p))
+    if r != 0:
+        raise ValueError("weighted SSSP needs non-negative edge weights")
+    return label
+
+
+def sssp_weighted_check(nv, col_end, src, weight, label, source):
+    return cpu.lux_sssp_weighted_check(ctypes.c_uint32(nv),
+                                       ptr(col_end, u64p), ptr(src, u32p),
+                                       ptr(weight, i32p), ptr(label, u32p),
+                                       ctypes.c_uint32(source))
 
 
 def cf_init(nv, K):

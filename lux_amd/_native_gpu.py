@@ -185,6 +185,59 @@ def blocked_scatter(stream, ep, col, row_ptr_loc, vp, bounds, nb, cursor,
                                   dp(cursor), dp(out_col))
 
 
+PULL_MIN_W = 4  # weighted SSSP (min-plus); served by pull_iter_w
+
+
+def pull_iter_w(stream, n0, bin0, n1, bin1, n2, bin2, nbig, bin2v, row_ptr,
+                col, wgt, oldv, newv, row_left, row_u32=0):
+    """Weighted SSSP dense sweep: wgt[j] is the weight of edge col[j]."""
+    lib().lux_gpu_pull_iter_w(_u64(stream), _u32(n0), dp(bin0), _u32(n1),
+                              dp(bin1), _u32(n2), dp(bin2), _u32(nbig),
+                              dp(bin2v), dp(row_ptr), ctypes.c_int(row_u32),
+                              dp(col), dp(wgt), dp(oldv), dp(newv),
+                              _u32(row_left))
+
+
+def blocked_scatter_w(stream, ep, col, weight, row_ptr_loc, vp, bounds, nb,
+                      cursor, out_col, out_w, lo=0, hi=0xFFFFFFFF):
+    lib().lux_gpu_blocked_scatter_w(_u64(stream), _u64(ep), dp(col),
+                                    dp(weight), dp(row_ptr_loc), _u32(vp),
+                                    dp(bounds), ctypes.c_int(nb), _u32(lo),
+                                    _u32(hi), dp(cursor), dp(out_col),
+                                    dp(out_w))
+
+
+def hash_weights(stream, ep, col, row_ptr_loc, vp, row_left, seed, wmax,
+                 weight):
+    lib().lux_gpu_hash_weights(_u64(stream), _u64(ep), dp(col),
+                               dp(row_ptr_loc), _u32(vp), _u32(row_left),
+                               _u64(seed), _u32(wmax), dp(weight))
+
+
+def csr_scatter_w(stream, ep, col, weight, row_ptr_loc, vp, row_left, cursor,
+                  push_edge):
+    lib().lux_gpu_csr_scatter_w(_u64(stream), _u64(ep), dp(col), dp(weight),
+                                dp(row_ptr_loc), _u32(vp), _u32(row_left),
+                                dp(cursor), dp(push_edge))
+
+
+def push_chunk_scatter_w(stream, new_dense, items, counter, max_items,
+                         push_row_ptr, push_edge, old_labels, snapshot,
+                         new_labels, my_row_left, new_seg, capacity):
+    lib().lux_gpu_push_chunk_scatter_w(
+        _u64(stream), ctypes.c_int(new_dense), dp(items), dp(counter),
+        _u32(max_items), dp(push_row_ptr), dp(push_edge), dp(old_labels),
+        dp(snapshot), dp(new_labels), _u32(my_row_left), dp(new_seg),
+        _u32(capacity))
+
+
+def check_w(stream, vp, row_left, row_ptr_loc, col, weight, labels, source,
+            mistakes):
+    lib().lux_gpu_check_w(_u64(stream), _u32(vp), _u32(row_left),
+                          dp(row_ptr_loc), dp(col), dp(weight), dp(labels),
+                          _u32(source), dp(mistakes))
+
+
 def pull_finish_pr(stream, vp, newv, deg, row_left, init_rank):
     lib().lux_gpu_pull_finish_pr(_u64(stream), _u32(vp), dp(newv), dp(deg),
                                  _u32(row_left), ctypes.c_float(init_rank))

@@ -26,6 +26,8 @@ class AppArgs:
         self.labelprop = False  # components: reference-parity label prop
         #                         (default is the union-find fast path)
         self.synthetic = None  # e.g. "rmat:20:1000000"
+        self.weighted = False  # sssp: min-plus over the edge weights
+        self.wmax = 16  # sssp -weighted -synthetic: hash weights in [1, wmax]
 
 
 def parse_input_args(argv):
@@ -55,6 +57,10 @@ def parse_input_args(argv):
             a.labelprop = True; i += 1
         elif f == "-synthetic":
             a.synthetic = argv[i + 1]; i += 2
+        elif f == "-weighted":
+            a.weighted = True; i += 1
+        elif f == "-wmax":
+            a.wmax = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \
@@ -115,6 +121,18 @@ def load_part(a, device, weighted=False, sym=False):
                                               int(parts[3]), ws, rk,
                                               device=device)
     raise SystemExit("need -file graph.lux or -synthetic kind:args")
+
+
+def attach_hash_weights(a, part):
+    """-weighted with -synthetic rmat:... / rmat_folded:...: give the part
+    endpoint-hash weights in [1, -wmax] (GraphPart.hash_weights, the
+    builders' default seed 1). Other specs carry their own weights."""
+    kind = (a.synthetic or "").split(":")[0]
+    if kind not in ("rmat", "rmat_folded"):
+        raise SystemExit("-weighted needs -file with weights or -synthetic "
+                         "rmat:... / rmat_folded:...")
+    part.hash_weights(a.wmax)
+    return part
 
 
 def print_memory_estimate(nv, ne, nparts, weighted=False, k=1):

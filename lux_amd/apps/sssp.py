@@ -1,12 +1,14 @@
 """SSSP app driver (reference parity: sssp/sssp.cc; unweighted hop
-distances, push model with adaptive frontiers)."""
+distances, push model with adaptive frontiers). -weighted runs min-plus
+relaxation over the graph's edge weights instead (-file: the .lux weights;
+-synthetic rmat/rmat_folded: endpoint-hash weights in [1, -wmax])."""
 import sys
 
 from .. import dist as dx
 from ..engine import GraphPart
 from ..push_engine import PushEngine
-from .common import (ElapsedTimer, load_part, parse_input_args,
-                     print_memory_estimate)
+from .common import (ElapsedTimer, attach_hash_weights, load_part,
+                     parse_input_args, print_memory_estimate)
 
 
 class SSSPBench:
@@ -41,10 +43,15 @@ def main(argv=None):
     local = dx.env_local_rank()
     torch.cuda.set_device(local)
     device = f"cuda:{local}"
-    part = load_part(a, device)
+    # -weighted -file: the loader raises on a file without weights
+    part = load_part(a, device, weighted=a.weighted and bool(a.file))
+    if a.weighted and not a.file:
+        attach_hash_weights(a, part)
     if dx.rank() == 0:
-        print_memory_estimate(part.nv, part.ne, dx.world_size())
-    eng = PushEngine(part, PushEngine.MODE_MIN, source=a.start)
+        print_memory_estimate(part.nv, part.ne, dx.world_size(),
+                              weighted=a.weighted)
+    eng = PushEngine(part, PushEngine.MODE_MIN, source=a.start,
+                     weighted=a.weighted)
     with ElapsedTimer():
         iters = eng.run()
     if dx.rank() == 0:

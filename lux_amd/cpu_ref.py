@@ -43,6 +43,24 @@ def cc_check(g: Graph, label: np.ndarray) -> int:
     return nat.cc_check(g.nv, g.ne, g.col_end, g.src, label)
 
 
+def sssp_weighted(g: Graph, source: int) -> np.ndarray:
+    """Exact shortest distances over g.weight (non-negative i32), u32 with
+    INF for unreachable vertices: binary-heap Dijkstra with the engines'
+    saturation, cand = min(label[u] + w, 0xFFFFFFFE)."""
+    assert g.weight is not None, "weighted SSSP needs g.weight"
+    return nat.sssp_weighted_cpu(
+        g.nv, g.ne, g.col_end, g.src,
+        np.ascontiguousarray(g.weight, np.int32), source)
+
+
+def sssp_weighted_check(g: Graph, label: np.ndarray, source: int) -> int:
+    """Edges with label[v] > sat(label[u] + w) for finite label[u], plus
+    one if label[source] != 0 (PushEngine.check's weighted invariant)."""
+    return int(nat.sssp_weighted_check(
+        g.nv, g.col_end, g.src, np.ascontiguousarray(g.weight, np.int32),
+        np.ascontiguousarray(label, np.uint32), source))
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

@@ -60,6 +60,11 @@ def run_pull_sweeps(part, mode, oldv, newv, deg, init_rank, subset=None):
     vertex range (requires the rank-aligned blocked build)."""
     s = _stream()
     blocks = getattr(part, "blocks", None)
+    weighted = mode == ng.PULL_MIN_W  # weighted SSSP route (pull_iter_w)
+    if weighted:
+        assert part.weight is not None, "PULL_MIN_W needs part.weight"
+        assert not blocks or "weight" in blocks[0], \
+            "blocked CSC built without weights: prepare_pull(weighted=True)"
     if blocks:
         for blk in blocks:
             if subset == "local" and not blk["local"]:
@@ -69,6 +74,13 @@ def run_pull_sweeps(part, mode, oldv, newv, deg, init_rank, subset=None):
             if isinstance(subset, tuple) and subset[0] == "peer" \
                     and blk.get("owner") != subset[1]:
                 continue
+            if weighted:
+                ng.pull_iter_w(s, blk["n0"], blk["bin0"], blk["n1"],
+                               blk["bin1"], blk["n2"], blk["bin2"],
+                               blk["nbig"], blk["bin2v"], blk["row_ptr"],
+                               blk["col"], blk["weight"], oldv, newv,
+                               part.row_left, row_u32=blk.get("row_u32", 0))
+                continue
             ng.pull_iter(s, mode, blk["n0"], blk["bin0"], blk["n1"],
                          blk["bin1"], blk["n2"], blk["bin2"], blk["nbig"],
                          blk["bin2v"], blk["row_ptr"], blk["col"], oldv,
@@ -76,6 +88,12 @@ def run_pull_sweeps(part, mode, oldv, newv, deg, init_rank, subset=None):
                          row_u32=blk.get("row_u32", 0))
     else:
         assert subset is None, "subset sweeps need the blocked CSC"
+        if weighted:
+            ng.pull_iter_w(s, part.n0, part.bin0, part.n1, part.bin1,
+                           part.n2, part.bin2, part.nbig, part.bin2v,
+                           part.row_ptr, part.col, part.weight, oldv, newv,
+                           part.row_left)
+            return
         ng.pull_iter(s, mode, part.n0, part.bin0, part.n1, part.bin1,
                      part.n2, part.bin2, part.nbig, part.bin2v, part.row_ptr,
                      part.col, oldv, newv, deg, part.row_left, init_rank)
@@ -124,7 +142,8 @@ def seed_pull(part, mode, oldv, newv):
 def run_pull(part, mode, oldv, newv, deg, init_rank, seed=True):
     """One full synchronous pull iteration over this rank's partition.
     Contract: seed newv (PR: zeros, labels: the old label slice), fold-sweep
-    the (blocked) CSC, then for PR apply the epilogue once."""
+    the (blocked) CSC, then for PR apply the epilogue once. mode
+    ng.PULL_MIN_W is the weighted SSSP (min-plus) sweep over part.weight."""
     if seed:
         seed_pull(part, mode, oldv, newv)
     run_pull_sweeps(part, mode, oldv, newv, deg, init_rank)
@@ -236,6 +255,21 @@ class DeviceCSC:
         if g.weight is not None:
             w = torch.from_numpy(g.weight).to(device)
         return cls(g.nv, g.ne, col_end, src, w)
+
+    def hash_weights(self, wmax, seed=1):
+        """Attach endpoint-hash weights in [1, wmax] (edge_hash_weight,
+        src/include/lux/rmat.h) — the device twin of Graph.hash_weights.
+        Fills and returns self.weight (i32[ne])."""
+        assert wmax >= 1
+        device = self.src.device
+        s = _stream()
+        row_ptr = torch.empty(self.nv + 1, dtype=U64, device=device)
+        ng.local_row_ptr(s, self.nv, 0, self.col_end, row_ptr)
+        self.weight = torch.empty(max(self.ne, 1), dtype=U32, device=device)
+        ng.hash_weights(s, self.ne, self.src, row_ptr, self.nv, 0, seed, wmax,
+                        self.weight)
+        torch.cuda.synchronize()
+        return self.weight
 
 
 class GraphPart:
@@ -428,6 +462,18 @@ class GraphPart:
                 np.ascontiguousarray(w_slice)).to(device)
         return p
 
+    def hash_weights(self, wmax, seed=1):
+        """Endpoint-hash weights for this rank's edge slice (same values as
+        DeviceCSC.hash_weights / Graph.hash_weights on the full graph).
+        Fills and returns self.weight (i32[ep])."""
+        assert wmax >= 1
+        self.weight = torch.empty(max(self.ep, 1), dtype=U32,
+                                  device=self.device)
+        ng.hash_weights(_stream(), self.ep, self.col, self.row_ptr, self.vp,
+                        self.row_left, seed, wmax, self.weight)
+        torch.cuda.synchronize()
+        return self.weight
+
     def build_bins(self):
         if hasattr(self, "bin0"):
             return
@@ -451,13 +497,24 @@ class GraphPart:
                                self.row_right_all[q] + 1}
         return sorted(bounds)
 
-    def prepare_pull(self, force_shift=None):
+    def prepare_pull(self, force_shift=None, weighted=False):
         """Build degree bins and the src-blocked CSC where it pays: when
         the gather window (nv*4 B) exceeds the 256 MiB Infinity Cache
         (LLC-resident sweeps), or when partitioned (rank-local block for
-        comm/compute overlap)."""
+        comm/compute overlap). weighted: the blocked CSC also carries
+        self.weight, one view per window next to its col view (weighted
+        SSSP pull); a blocked CSC built earlier without weights is built
+        again with them."""
         self.build_bins()
-        if getattr(self, "blocks", None) is not None:
+        weighted = bool(weighted) and self.weight is not None
+        blocks = getattr(self, "blocks", None)
+        if blocks is not None:
+            if not weighted or not blocks or "weight" in blocks[0]:
+                return
+            # same bounds as the existing build, now with weights
+            bounds = self._blk_bounds
+            self.blocks = None
+            self.build_blocked(bounds, weighted=True)
             return
         shift = force_shift if force_shift is not None else int(
             __import__("os").environ.get("LUX_BLOCK_SHIFT", LLC_BLOCK_SHIFT))
@@ -486,7 +543,7 @@ class GraphPart:
                 and self.nparts == 1:
             self.blocks = None
             return
-        self.build_blocked(bounds)
+        self.build_blocked(bounds, weighted=weighted)
 
     def prepare_pull_slots(self):
         """Slot streams + active-row list for the PageRank sweeps (built
@@ -585,13 +642,15 @@ class GraphPart:
         self.stream_bytes = torch.cuda.memory_allocated(device) - before
         self.slot_bytes += self.stream_bytes
 
-    def build_blocked(self, bounds):
+    def build_blocked(self, bounds, weighted=False):
         """Src-blocked CSC build, processed in window GROUPS sized so the
         transient (block, row) slot table (counts 4 B + cursor 8 B per
         slot) fits free HBM — 32 MB windows therefore hold at every
         scale (the full table at RMAT-29 x 1 GPU would be 384 GB). Each
         extra group costs one more filtered pass over the edge list.
-        LUX_BLOCK_GROUP_SLOTS caps the slot budget (tests)."""
+        LUX_BLOCK_GROUP_SLOTS caps the slot budget (tests). weighted: the
+        scatter moves each edge's weight to the same claimed slot as its
+        col entry, and every window gets a "weight" view next to "col"."""
         import os
         device = self.device
         s = _stream()
@@ -603,6 +662,10 @@ class GraphPart:
             cap = int(max(free - 4 * ep - (2 << 30), 1 << 30) * 0.85) // 12
         bpg = sb if not cap else max(1, min(sb, cap // max(vp, 1)))
         blk_col = torch.empty(max(ep, 1), dtype=U32, device=device)
+        weighted = bool(weighted) and self.weight is not None
+        blk_w = torch.empty(max(ep, 1), dtype=U32, device=device) \
+            if weighted else None
+        self._blk_bounds = bounds
         self.blocks = []
         global_begin = 0
         for g0 in range(0, sb, bpg):
@@ -627,9 +690,16 @@ class GraphPart:
             torch.cuda.empty_cache()
             if global_begin:
                 cursor += global_begin  # offsets into the shared blk_col
-            ng.blocked_scatter(s, ep, self.col, self.row_ptr, vp, bounds_g,
-                               nb + 1, cursor.narrow(0, 0, slots), blk_col,
-                               lo=bounds[g0], hi=bounds[g1])
+            if weighted:
+                ng.blocked_scatter_w(s, ep, self.col, self.weight,
+                                     self.row_ptr, vp, bounds_g, nb + 1,
+                                     cursor.narrow(0, 0, slots), blk_col,
+                                     blk_w, lo=bounds[g0], hi=bounds[g1])
+            else:
+                ng.blocked_scatter(s, ep, self.col, self.row_ptr, vp,
+                                   bounds_g, nb + 1,
+                                   cursor.narrow(0, 0, slots), blk_col,
+                                   lo=bounds[g0], hi=bounds[g1])
             ends = cursor.narrow(0, 0, slots)  # post-scatter = end offsets
             begin = global_begin
             for b in range(nb):
@@ -663,10 +733,14 @@ class GraphPart:
                                         bin0=b0, bin1=b1, bin2=b2,
                                         bin2v=b2v, local=local,
                                         owner=owner))
+                if weighted:
+                    self.blocks[-1]["weight"] = blk_w.narrow(0, begin,
+                                                             end - begin)
                 begin = end
             global_begin = int(ends[slots - 1].item())
             del ends, cursor
         self._blk_col = blk_col  # keep the narrow()s' base alive
+        self._blk_w = blk_w
 
 
 def _maybe_halo(part):

@@ -84,6 +84,16 @@ class Graph:
         col_end, csrc, cw = nat.edges_to_csc(nv, src, dst, w)
         return cls(nv, len(src), col_end, csrc, cw)
 
+    def hash_weights(self, wmax, seed=1):
+        """Attach deterministic weights in [1, wmax] that depend only on
+        each edge's endpoints (edge_hash_weight, src/include/lux/rmat.h);
+        DeviceCSC.hash_weights / GraphPart.hash_weights give the same
+        values on the device. Fills and returns g.weight."""
+        assert wmax >= 1
+        self.weight = nat.hash_weights(self.nv, self.col_end, self.src,
+                                       wmax, seed)
+        return self.weight
+
     # ---- IO ----
     def save(self, path):
         nat.io_write(path, self.nv, self.ne, self.col_end, self.src,

@@ -88,18 +88,42 @@ class PushEngine:
     MODE_MIN = 1  # SSSP
     MODE_MAX = 2  # CC
 
-    def __init__(self, part: GraphPart, mode, source=0):
+    def __init__(self, part: GraphPart, mode, source=0, weighted=False):
+        """weighted (MODE_MIN only): min-plus relaxation over part.weight
+        (non-negative i32; ValueError on a negative one, agreed across
+        ranks). Labels are exact shortest distances, saturating at
+        0xFFFFFFFE; unreachable vertices keep INF. A label can improve in
+        several iterations, so this mode uses neither the visited bitmap
+        nor the pull kernels' settled-row skip."""
         self.part = part
         self.mode = mode
         self.is_min = mode == self.MODE_MIN
+        self.weighted = bool(weighted)
         device = part.device
         self.device = device
         s = _stream()
         p = part
+        if self.weighted:
+            assert self.is_min, "weighted relaxation is MODE_MIN (SSSP) only"
+            assert part.weight is not None, "weighted SSSP needs part.weight"
+            # each rank checks its own slice; one all-reduce of the flag
+            # makes every rank raise, or none
+            neg = (part.weight.narrow(0, 0, p.ep) < 0).any().to(U32) \
+                .reshape(1) if p.ep else torch.zeros(1, dtype=U32,
+                                                     device=device)
+            dx.all_reduce_sum_(neg)
+            if int(neg.item()):
+                raise ValueError("weighted SSSP needs non-negative edge "
+                                 "weights")
+        self._pull_mode = ng.PULL_MIN_W if self.weighted else (
+            ng.PULL_MIN if self.is_min else ng.PULL_MAX)
 
         # pull bins (+ src-blocked CSC when nv is LLC-large) for the
-        # dense fallback
-        part.prepare_pull()
+        # dense fallback; the weighted one carries the weights per window
+        if self.weighted:
+            part.prepare_pull(weighted=True)
+        else:
+            part.prepare_pull()
 
         # ---- push CSR: all nv sources -> my-partition dsts ----
         deg_src = torch.zeros(p.nv, dtype=U32, device=device)
@@ -111,9 +135,18 @@ class PushEngine:
         self.push_row_ptr = torch.empty(p.nv + 1, dtype=U64, device=device)
         ng.local_row_ptr(s, p.nv, 0, ends, self.push_row_ptr)
         cursor = self.push_row_ptr[:p.nv].clone()
-        self.push_col = torch.empty(max(p.ep, 1), dtype=U32, device=device)
-        ng.csr_scatter(s, p.ep, p.col, p.row_ptr, p.vp, p.row_left, cursor,
-                       self.push_col)
+        if self.weighted:
+            # interleaved {global dst, weight} per out-edge (uint2[ep])
+            self.push_col = None
+            self.push_edge = torch.empty(2 * max(p.ep, 1), dtype=U32,
+                                         device=device)
+            ng.csr_scatter_w(s, p.ep, p.col, p.weight, p.row_ptr, p.vp,
+                             p.row_left, cursor, self.push_edge)
+        else:
+            self.push_col = torch.empty(max(p.ep, 1), dtype=U32,
+                                        device=device)
+            ng.csr_scatter(s, p.ep, p.col, p.row_ptr, p.vp, p.row_left,
+                           cursor, self.push_col)
         # global out-degrees (deg_src summed over ranks); keep only my
         # partition's slice — it prices the NEW frontier's out-edge volume
         # in the meta record (the exact push-vs-pull input)
@@ -157,9 +190,11 @@ class PushEngine:
         # hop-SSSP (level-synchronous BFS) visited bitmap: push discovery
         # is a test-and-set against vp/8 bytes (L2-resident) instead of an
         # atomicMin against the 4*vp label array (push.hip BFS_BITS path);
-        # rebuilt from labels after pull iterations
+        # rebuilt from labels after pull iterations. Weighted SSSP has no
+        # one-shot discovery: no bitmap, label atomics only.
         self.visited = torch.empty((p.vp + 31) // 32, dtype=U32,
-                                   device=device) if self.is_min else None
+                                   device=device) \
+            if self.is_min and not self.weighted else None
         self._bits_stale = True
 
         # ---- labels + frontier state ----
@@ -252,6 +287,26 @@ class PushEngine:
         self._sync_labels()
         return self.labels
 
+    def _scatter(self, s, new_dense, bits):
+        """Chunk scatter over the expanded work items: the min-plus kernel
+        on the interleaved CSR when weighted, else the hop / CC kernel."""
+        p = self.part
+        if self.weighted:
+            ng.push_chunk_scatter_w(s, int(new_dense), self.items,
+                                    self.item_counter, self.max_items,
+                                    self.push_row_ptr, self.push_edge,
+                                    self.labels, self.snapshot,
+                                    self.labels_part, p.row_left,
+                                    self.new_seg, self.capacity)
+            return
+        ng.push_chunk_scatter(s, int(self.is_min), int(new_dense),
+                              self.items, self.item_counter,
+                              self.max_items, self.push_row_ptr,
+                              self.push_col, self.labels, self.snapshot,
+                              self.labels_part, p.row_left,
+                              self.new_seg, self.capacity,
+                              visited_bits=bits)
+
     def _single_body(self, pull, new_dense):
         """One complete world-1 iteration body: compute + fixups + the
         device-side "exchange" (full-size self copies + meta). Every op
@@ -261,8 +316,8 @@ class PushEngine:
         self.snapshot.copy_(self.labels_part)
         self.new_seg[:8].copy_(self._hdr_zero)
         if pull:
-            mode = ng.PULL_MIN if self.is_min else ng.PULL_MAX
-            run_pull(p, mode, self.labels, self.labels_part, None, 0.0)
+            run_pull(p, self._pull_mode, self.labels, self.labels_part,
+                     None, 0.0)
             counter = None
         else:
             self.item_counter.zero_()
@@ -272,13 +327,7 @@ class PushEngine:
                                     self.item_counter, self.max_items)
             bits = self.visited if self.visited is not None and p.vp > 0 \
                 else None
-            ng.push_chunk_scatter(s, int(self.is_min), int(new_dense),
-                                  self.items, self.item_counter,
-                                  self.max_items, self.push_row_ptr,
-                                  self.push_col, self.labels, self.snapshot,
-                                  self.labels_part, p.row_left,
-                                  self.new_seg, self.capacity,
-                                  visited_bits=bits)
+            self._scatter(s, new_dense, bits)
             counter = self.item_counter
         if pull or new_dense:
             ng.build_bitmap(s, p.vp, self.snapshot, self.labels_part,
@@ -422,8 +471,8 @@ class PushEngine:
         if pull_fallback:
             new_dense = True
             self._sync_labels()  # pull reads every vertex's label
-            mode = ng.PULL_MIN if self.is_min else ng.PULL_MAX
-            run_pull(p, mode, self.labels, self.labels_part, None, 0.0)
+            run_pull(p, self._pull_mode, self.labels, self.labels_part,
+                     None, 0.0)
             self._bits_stale = True  # pull writes labels directly
             item_counter = None
         else:
@@ -460,13 +509,7 @@ class PushEngine:
                                         self.visited)
                     self._bits_stale = False
                 bits = self.visited
-            ng.push_chunk_scatter(s, int(self.is_min), int(new_dense),
-                                  self.items, self.item_counter,
-                                  self.max_items, self.push_row_ptr,
-                                  self.push_col, self.labels, self.snapshot,
-                                  self.labels_part, p.row_left,
-                                  self.new_seg, self.capacity,
-                                  visited_bits=bits)
+            self._scatter(s, new_dense, bits)
             item_counter = self.item_counter
 
         # ---- frontier fix-ups + meta, all device-side ----
@@ -536,7 +579,11 @@ class PushEngine:
         p = self.part
         self._sync_labels()
         mistakes = torch.zeros(1, dtype=U64, device=self.device)
-        ng.check(_stream(), int(self.is_min), p.vp, p.row_left, p.row_ptr,
-                 p.col, self.labels, mistakes)
+        if self.weighted:
+            ng.check_w(_stream(), p.vp, p.row_left, p.row_ptr, p.col,
+                       p.weight, self.labels, self.source, mistakes)
+        else:
+            ng.check(_stream(), int(self.is_min), p.vp, p.row_left,
+                     p.row_ptr, p.col, self.labels, mistakes)
         dx.all_reduce_sum_(mistakes)
         return int(mistakes.cpu().item())

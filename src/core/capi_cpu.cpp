@@ -26,6 +26,14 @@ int sssp_cpu(const HostCSC& g, V_ID source, V_ID* label_out);
 int cc_cpu(const HostCSC& g, V_ID* label_out);
 E_ID sssp_check(const HostCSC& g, const V_ID* label);
 E_ID cc_check(const HostCSC& g, const V_ID* label);
+void hash_weights(V_ID nv, const E_ID* col_end, const V_ID* src,
+                  uint64_t seed, uint32_t wmax, WeightType* weight);
+int sssp_weighted_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+                      const WeightType* weight, V_ID source,
+                      V_ID* label_out);
+E_ID sssp_weighted_check(V_ID nv, const E_ID* col_end, const V_ID* src,
+                         const WeightType* weight, const V_ID* label,
+                         V_ID source);
 void cf_init(V_ID nv, int K, float* vec);
 void cf_iter_part(V_ID row_left, V_ID row_right, E_ID col_left,
                   const E_ID* col_end, const V_ID* src, const WeightType* w,
@@ -210,6 +218,21 @@ uint64_t lux_cc_check(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                       const uint32_t* src, const uint32_t* label) {
   HostCSC g = view_csc(nv, ne, col_end, src, nullptr);
   return cc_check(g, label);
+}
+void lux_hash_weights(uint32_t nv, const uint64_t* col_end,
+                      const uint32_t* src, uint64_t seed, uint32_t wmax,
+                      int32_t* weight) {
+  hash_weights(nv, col_end, src, seed, wmax, weight);
+}
+int lux_sssp_weighted_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                          const uint32_t* src, const int32_t* weight,
+                          uint32_t source, uint32_t* label_out) {
+  return sssp_weighted_cpu(nv, ne, col_end, src, weight, source, label_out);
+}
+uint64_t lux_sssp_weighted_check(uint32_t nv, const uint64_t* col_end,
+                                 const uint32_t* src, const int32_t* weight,
+                                 const uint32_t* label, uint32_t source) {
+  return sssp_weighted_check(nv, col_end, src, weight, label, source);
 }
 void lux_cf_init(uint32_t nv, int K, float* vec) { cf_init(nv, K, vec); }
 void lux_cf_iter_part(uint32_t row_left, uint32_t row_right,

@@ -22,9 +22,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
+#include <queue>
+#include <utility>
 #include <vector>
 
 #include "lux/graph.h"
+#include "lux/rmat.h"
 
 namespace lux {
 
@@ -163,6 +167,93 @@ E_ID cc_check(const HostCSC& g, const V_ID* label) {
   for (V_ID v = 0; v < g.nv; v++)
     for (E_ID i = g.row_begin(v); i < g.row_end(v); i++)
       if (label[v] < label[g.src[i]]) mistakes++;
+  return mistakes;
+}
+
+// ---------- Weighted SSSP (min-plus) ----------
+// Weights are the graph's i32 weights read as non-negative integers.
+// Relaxation saturates: cand = min(u64(label[u]) + w, 0xFFFFFFFE), so a
+// finite distance never turns into INF_LABEL or wraps.
+
+static inline V_ID sat_add_label(V_ID lab, WeightType w) {
+  uint64_t c = (uint64_t)lab + (uint64_t)(uint32_t)w;
+  return c > 0xFFFFFFFEull ? 0xFFFFFFFEu : (V_ID)c;
+}
+
+// weight[i] = edge_hash_weight(seed, src[i], dst of edge i, wmax)
+void hash_weights(V_ID nv, const E_ID* col_end, const V_ID* src,
+                  uint64_t seed, uint32_t wmax, WeightType* weight) {
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    E_ID e = col_end[v];
+    for (E_ID i = b; i < e; i++)
+      weight[i] = edge_hash_weight(seed, src[i], v, wmax);
+    b = e;
+  }
+}
+
+// Exact binary-heap Dijkstra (the CSC is turned into out-edge lists
+// first). Returns -1 on a negative weight.
+int sssp_weighted_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+                      const WeightType* weight, V_ID source,
+                      V_ID* label_out) {
+  for (E_ID i = 0; i < ne; i++)
+    if (weight[i] < 0) return -1;
+  std::vector<E_ID> out_ptr((size_t)nv + 1, 0);
+  for (E_ID i = 0; i < ne; i++) out_ptr[src[i] + 1]++;
+  for (V_ID v = 0; v < nv; v++) out_ptr[v + 1] += out_ptr[v];
+  std::vector<V_ID> out_dst(ne);
+  std::vector<WeightType> out_w(ne);
+  {
+    std::vector<E_ID> cur(out_ptr.begin(), out_ptr.end() - 1);
+    E_ID b = 0;
+    for (V_ID v = 0; v < nv; v++) {
+      E_ID e = col_end[v];
+      for (E_ID i = b; i < e; i++) {
+        E_ID pos = cur[src[i]]++;
+        out_dst[pos] = v;
+        out_w[pos] = weight[i];
+      }
+      b = e;
+    }
+  }
+  for (V_ID v = 0; v < nv; v++) label_out[v] = INF_LABEL;
+  label_out[source] = 0;
+  using Ent = std::pair<V_ID, V_ID>;  // (distance, vertex)
+  std::priority_queue<Ent, std::vector<Ent>, std::greater<Ent>> heap;
+  heap.push({0, source});
+  while (!heap.empty()) {
+    Ent top = heap.top();
+    heap.pop();
+    V_ID u = top.second;
+    if (top.first != label_out[u]) continue;  // stale entry
+    for (E_ID i = out_ptr[u]; i < out_ptr[u + 1]; i++) {
+      V_ID cand = sat_add_label(top.first, out_w[i]);
+      if (cand < label_out[out_dst[i]]) {
+        label_out[out_dst[i]] = cand;
+        heap.push({cand, out_dst[i]});
+      }
+    }
+  }
+  return 0;
+}
+
+// Edges with label[v] > sat(label[u] + w) where label[u] is finite, plus
+// one if label[source] != 0 (the device check's invariant).
+E_ID sssp_weighted_check(V_ID nv, const E_ID* col_end, const V_ID* src,
+                         const WeightType* weight, const V_ID* label,
+                         V_ID source) {
+  E_ID mistakes = label[source] != 0 ? 1 : 0;
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    E_ID e = col_end[v];
+    for (E_ID i = b; i < e; i++) {
+      V_ID sl = label[src[i]];
+      if (sl != INF_LABEL && label[v] > sat_add_label(sl, weight[i]))
+        mistakes++;
+    }
+    b = e;
+  }
   return mistakes;
 }
 

@@ -243,6 +243,45 @@ __global__ void blocked_scatter_kernel(uint64_t ep, const V_ID* col,
   }
 }
 
+// blocked_scatter_kernel carrying the weights: col and its weight land in
+// the same claimed slot, so the per-window weight arrays index like the
+// per-window col arrays whatever order the cursor hands out.
+__global__ void blocked_scatter_w_kernel(uint64_t ep, const V_ID* col,
+                                         const WeightType* weight,
+                                         const E_ID* row_ptr_loc, V_ID vp,
+                                         const V_ID* bounds, int nb,
+                                         V_ID lo, V_ID hi,
+                                         unsigned long long* cursor,
+                                         V_ID* out_col, WeightType* out_w) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < ep;
+       j += stride) {
+    V_ID c = col[j];
+    if (c < lo || c >= hi) continue;
+    V_ID v = row_of_edge(row_ptr_loc, vp, j);
+    uint32_t b = block_of(c, bounds, nb);
+    unsigned long long pos = atomicAdd(&cursor[(uint64_t)b * vp + v], 1ull);
+    out_col[pos] = c;
+    out_w[pos] = weight[j];
+  }
+}
+
+// ---------------- endpoint-hash weights (weighted SSSP synthetics) --------
+// weight[j] = edge_hash_weight(seed, col[j], dst row of j, wmax): one
+// thread per edge, dst row by binary search over the local row_ptr —
+// identical to the CPU Graph.hash_weights for full and sliced builds.
+__global__ void hash_weights_kernel(uint64_t ep, const V_ID* col,
+                                    const E_ID* row_ptr_loc, V_ID vp,
+                                    V_ID row_left, uint64_t seed,
+                                    uint32_t wmax, WeightType* weight) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < ep;
+       j += stride) {
+    V_ID v = row_of_edge(row_ptr_loc, vp, j);
+    weight[j] = edge_hash_weight(seed, col[j], v + row_left, wmax);
+  }
+}
+
 // ---------------- local row_ptr from global col_end slice ----------------
 
 __global__ void local_row_ptr_kernel(uint32_t vp, E_ID col_left,
@@ -399,6 +438,31 @@ void lux_gpu_blocked_scatter(uint64_t stream, uint64_t ep, const V_ID* col,
   hipLaunchKernelGGL(blocked_scatter_kernel, dim3(grid_for(ep)), dim3(BLOCK),
                      0, s, ep, col, row_ptr_loc, vp, bounds, nb, lo, hi,
                      cursor, out_col);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_blocked_scatter_w(uint64_t stream, uint64_t ep, const V_ID* col,
+                               const WeightType* weight,
+                               const E_ID* row_ptr_loc, V_ID vp,
+                               const V_ID* bounds, int nb, V_ID lo, V_ID hi,
+                               unsigned long long* cursor, V_ID* out_col,
+                               WeightType* out_w) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ep == 0 || vp == 0) return;
+  hipLaunchKernelGGL(blocked_scatter_w_kernel, dim3(grid_for(ep)),
+                     dim3(BLOCK), 0, s, ep, col, weight, row_ptr_loc, vp,
+                     bounds, nb, lo, hi, cursor, out_col, out_w);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_hash_weights(uint64_t stream, uint64_t ep, const V_ID* col,
+                          const E_ID* row_ptr_loc, V_ID vp, V_ID row_left,
+                          uint64_t seed, uint32_t wmax, WeightType* weight) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ep == 0 || vp == 0) return;
+  hipLaunchKernelGGL(hash_weights_kernel, dim3(grid_for(ep)), dim3(BLOCK), 0,
+                     s, ep, col, row_ptr_loc, vp, row_left, seed, wmax,
+                     weight);
   LUX_POST_LAUNCH(stream);
 }
 

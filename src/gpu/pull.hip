@@ -28,7 +28,8 @@ constexpr V_ID T1 = 32;
 constexpr V_ID T2 = 2048;
 constexpr V_ID CHUNK_EDGES = 8192;
 
-enum PullMode { PR_SUM = 0, LAB_MIN = 1, LAB_MAX = 2, CF_SGD = 3 };
+enum PullMode { PR_SUM = 0, LAB_MIN = 1, LAB_MAX = 2, CF_SGD = 3,
+                LAB_MIN_W = 4 };
 
 // ---------------- bin building ----------------
 
@@ -127,6 +128,26 @@ template <> struct Val<LAB_MAX> {
   }
 };
 
+// Weighted SSSP (min-plus): every edge maps its source label with its own
+// weight (mapw), labels keep improving over iterations, so no row is ever
+// skipped as settled. Weights are non-negative i32; the sum saturates at
+// 0xFFFFFFFE (a finite distance never becomes INF_LABEL or wraps).
+template <> struct Val<LAB_MIN_W> {
+  using T = uint32_t;
+  static constexpr bool SKIP_SETTLED = false;
+  static __device__ __forceinline__ T ident() { return INF_LABEL; }
+  static __device__ __forceinline__ T mapw(T s, WeightType w) {
+    if (s == INF_LABEL) return INF_LABEL;
+    unsigned long long c = (unsigned long long)s + (uint32_t)w;
+    return c > 0xFFFFFFFEull ? 0xFFFFFFFEu : (T)c;
+  }
+  static __device__ __forceinline__ T comb(T a, T b) { return a < b ? a : b; }
+  static __device__ __forceinline__ void atom(T* p, T v) { atomicMin(p, v); }
+  static __device__ __forceinline__ T reduce_wave(T v) {
+    return wave_reduce_min(v);
+  }
+};
+
 // Epilogue: PR computes (1-a)/nv + a*sum then stores /out_degree
 // (pagerank_gpu.cu:97-100); labels fold the dst's own old label in.
 template <PullMode M>
@@ -150,6 +171,12 @@ struct PullArgs {
   const V_ID* deg;       // u32[nv] out-degrees (PR) or null
   V_ID row_left;
   float init_rank;
+};
+
+// Weighted sweeps: wgt[j] is the weight of edge col[j] (same edge index,
+// for the plain CSC and for every src window of the blocked one).
+struct PullArgsW : PullArgs {
+  const WeightType* wgt;
 };
 
 // Result store for the non-atomic bins. The iteration contract: newv is
@@ -185,6 +212,45 @@ __device__ __forceinline__ typename Val<M>::T gather_range(
   }
   for (; j < e; j += step) a0 = V::comb(a0, V::map(oldv[col[j]]));
   return V::comb(V::comb(a0, a1), V::comb(a2, a3));
+}
+
+// gather_range with a per-edge weight: the same four-way pipeline, the
+// weights of a batch fetched next to its col entries (both coalesced in
+// the wave and chunk roles), then four independent label gathers.
+template <PullMode M>
+__device__ __forceinline__ typename Val<M>::T gather_range_w(
+    const typename Val<M>::T* oldv, const V_ID* col, const WeightType* wgt,
+    E_ID j, E_ID e, E_ID step) {
+  using V = Val<M>;
+  using T = typename V::T;
+  T a0 = V::ident(), a1 = V::ident(), a2 = V::ident(), a3 = V::ident();
+  for (; j + 3 * step < e; j += 4 * step) {
+    V_ID c0 = col[j], c1 = col[j + step], c2 = col[j + 2 * step],
+         c3 = col[j + 3 * step];
+    WeightType w0 = wgt[j], w1 = wgt[j + step], w2 = wgt[j + 2 * step],
+               w3 = wgt[j + 3 * step];
+    a0 = V::comb(a0, V::mapw(oldv[c0], w0));
+    a1 = V::comb(a1, V::mapw(oldv[c1], w1));
+    a2 = V::comb(a2, V::mapw(oldv[c2], w2));
+    a3 = V::comb(a3, V::mapw(oldv[c3], w3));
+  }
+  for (; j < e; j += step) a0 = V::comb(a0, V::mapw(oldv[col[j]], wgt[j]));
+  return V::comb(V::comb(a0, a1), V::comb(a2, a3));
+}
+
+// What a role body calls for its edge range: picked by the args type, so
+// the unweighted instantiations are the plain gather_range as before.
+template <PullMode M>
+__device__ __forceinline__ typename Val<M>::T gather_edges(
+    const PullArgs& a, const typename Val<M>::T* oldv, E_ID j, E_ID e,
+    E_ID step) {
+  return gather_range<M>(oldv, a.col, j, e, step);
+}
+template <PullMode M>
+__device__ __forceinline__ typename Val<M>::T gather_edges(
+    const PullArgsW& a, const typename Val<M>::T* oldv, E_ID j, E_ID e,
+    E_ID step) {
+  return gather_range_w<M>(oldv, a.col, a.wgt, j, e, step);
 }
 
 // ---- where a bin entry's output row and edge range come from ----
@@ -240,10 +306,10 @@ struct SlotRows {
 };
 
 // ---- bin0 role: thread per vertex (block `blk` of `nblk`) ----
-template <PullMode M, typename Src>
+template <PullMode M, typename Src, typename Args>
 __device__ __forceinline__ void pull_thread_role(uint32_t blk, uint32_t nblk,
                                                  uint32_t n0, const Src& src,
-                                                 const PullArgs& a) {
+                                                 const Args& a) {
   using V = Val<M>;
   using T = typename V::T;
   const T* oldv = (const T*)a.oldv;
@@ -256,16 +322,16 @@ __device__ __forceinline__ void pull_thread_role(uint32_t blk, uint32_t nblk,
       continue;  // settled hop label: newv keeps the seed
     E_ID b, e;
     src.range(i, v, b, e);
-    T acc = gather_range<M>(oldv, a.col, b, e, 1);
+    T acc = gather_edges<M>(a, oldv, b, e, 1);
     store_result<M>(&newv[v], acc);
   }
 }
 
 // ---- bin1 role: wave per vertex ----
-template <PullMode M, typename Src>
+template <PullMode M, typename Src, typename Args>
 __device__ __forceinline__ void pull_wave_role(uint32_t blk, uint32_t nblk,
                                                uint32_t n1, const Src& src,
-                                               const PullArgs& a) {
+                                               const Args& a) {
   using V = Val<M>;
   using T = typename V::T;
   const T* oldv = (const T*)a.oldv;
@@ -279,7 +345,7 @@ __device__ __forceinline__ void pull_wave_role(uint32_t blk, uint32_t nblk,
       continue;
     E_ID b, e;
     src.range(i, v, b, e);
-    T acc = gather_range<M>(oldv, a.col, b + lane, e, WAVE);
+    T acc = gather_edges<M>(a, oldv, b + lane, e, WAVE);
     acc = V::reduce_wave(acc);
     if (lane == 0)
       store_result<M>(&newv[v], acc);
@@ -289,10 +355,10 @@ __device__ __forceinline__ void pull_wave_role(uint32_t blk, uint32_t nblk,
 // ---- bin2 role: chunk accumulation (hubs) ----
 // Contains __syncthreads(): every thread of a workgroup must enter it
 // together (the callers pick the role from blockIdx.x alone).
-template <PullMode M, typename Src>
+template <PullMode M, typename Src, typename Args>
 __device__ __forceinline__ void pull_chunk_role(uint32_t blk, uint32_t nblk,
                                                 uint32_t n2, const Src& src,
-                                                const PullArgs& a) {
+                                                const Args& a) {
   using V = Val<M>;
   using T = typename V::T;
   __shared__ T lds[BLOCK / WAVE];
@@ -305,7 +371,7 @@ __device__ __forceinline__ void pull_chunk_role(uint32_t blk, uint32_t nblk,
       continue;
     E_ID b, e;
     src.range(i, v, chunk, b, e);
-    T acc = gather_range<M>(oldv, a.col, b + threadIdx.x, e, blockDim.x);
+    T acc = gather_edges<M>(a, oldv, b + threadIdx.x, e, blockDim.x);
     // block reduce (sum mode) or wave+lds fold (min/max)
     int lane = threadIdx.x & (WAVE - 1);
     int wid = threadIdx.x >> 6;
@@ -340,6 +406,31 @@ __global__ void pull_chunk_kernel(uint32_t n2, const uint2* bin2,
                                   PullArgs a) {
   pull_chunk_role<M>(blockIdx.x, gridDim.x, n2,
                      TableChunks<RowT>{bin2, (const RowT*)a.row_ptr}, a);
+}
+
+// Weighted twins of the three table kernels (LAB_MIN_W): same role bodies,
+// PullArgsW carries the weight array.
+template <typename RowT>
+__global__ void pull_thread_w_kernel(uint32_t n0, const V_ID* bin0,
+                                     PullArgsW a) {
+  pull_thread_role<LAB_MIN_W>(blockIdx.x, gridDim.x, n0,
+                              TableRows<RowT>{bin0, (const RowT*)a.row_ptr},
+                              a);
+}
+
+template <typename RowT>
+__global__ void pull_wave_w_kernel(uint32_t n1, const V_ID* bin1,
+                                   PullArgsW a) {
+  pull_wave_role<LAB_MIN_W>(blockIdx.x, gridDim.x, n1,
+                            TableRows<RowT>{bin1, (const RowT*)a.row_ptr}, a);
+}
+
+template <typename RowT>
+__global__ void pull_chunk_w_kernel(uint32_t n2, const uint2* bin2,
+                                    PullArgsW a) {
+  pull_chunk_role<LAB_MIN_W>(blockIdx.x, gridDim.x, n2,
+                             TableChunks<RowT>{bin2, (const RowT*)a.row_ptr},
+                             a);
 }
 
 // ---- slot streams: one launch per src window (PR_SUM) ----
@@ -633,6 +724,24 @@ static void pull_iter(hipStream_t s, uint32_t n0, const V_ID* bin0,
                        dim3(BLOCK), 0, s, n0, bin0, a);
 }
 
+template <typename RowT>
+static void pull_iter_w(hipStream_t s, uint32_t n0, const V_ID* bin0,
+                        uint32_t n1, const V_ID* bin1, uint32_t n2,
+                        const uint2* bin2, uint32_t nbig,
+                        const PullArgsW& a) {
+  if (nbig)
+    hipLaunchKernelGGL(pull_chunk_w_kernel<RowT>,
+                       dim3(n2 > MAX_GRID ? MAX_GRID : n2), dim3(BLOCK), 0, s,
+                       n2, bin2, a);
+  if (n1)
+    hipLaunchKernelGGL(pull_wave_w_kernel<RowT>,
+                       dim3(grid_for((uint64_t)n1 * WAVE)), dim3(BLOCK), 0, s,
+                       n1, bin1, a);
+  if (n0)
+    hipLaunchKernelGGL(pull_thread_w_kernel<RowT>, dim3(grid_for(n0)),
+                       dim3(BLOCK), 0, s, n0, bin0, a);
+}
+
 // PR epilogue over the whole partition: pr = (1-a)/nv + a*sum, stored
 // divided by out-degree (pagerank_gpu.cu:97-100, :255-259). Covers rows
 // with no in-edges too (sum stays 0 from the seed).
@@ -715,6 +824,27 @@ void lux_gpu_pull_iter(uint64_t stream, int mode, uint32_t n0,
     case 2: LUX_PI(LAB_MAX); break;
   }
 #undef LUX_PI
+  LUX_POST_LAUNCH(stream);
+}
+
+// Weighted SSSP dense sweep (LAB_MIN_W): newv[v] = min(newv[v], min over
+// in-edges j of sat(oldv[col[j]] + wgt[j])), INF sources skipped. wgt is
+// indexed like col. Same bins, row tables and seed contract as
+// lux_gpu_pull_iter's label modes; no settled-row skip.
+void lux_gpu_pull_iter_w(uint64_t stream, uint32_t n0, const V_ID* bin0,
+                         uint32_t n1, const V_ID* bin1, uint32_t n2,
+                         const uint2* bin2, uint32_t nbig,
+                         const V_ID* bin2v, const void* row_ptr, int row_u32,
+                         const V_ID* col, const WeightType* wgt,
+                         const uint32_t* oldv, uint32_t* newv,
+                         V_ID row_left) {
+  hipStream_t s = (hipStream_t)stream;
+  (void)bin2v;
+  PullArgsW a{{row_ptr, col, oldv, newv, nullptr, row_left, 0.0f}, wgt};
+  if (row_u32)
+    pull_iter_w<uint32_t>(s, n0, bin0, n1, bin1, n2, bin2, nbig, a);
+  else
+    pull_iter_w<uint64_t>(s, n0, bin0, n1, bin1, n2, bin2, nbig, a);
   LUX_POST_LAUNCH(stream);
 }
 

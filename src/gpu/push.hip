@@ -568,6 +568,172 @@ __global__ void check_kernel(V_ID vp, V_ID row_left, const E_ID* row_ptr_loc,
   if (threadIdx.x == 0 && cnt) atomicAdd(mistakes, cnt);
 }
 
+// ---------------- weighted SSSP (min-plus) ----------------
+// Edge weights are the graph's i32 weights read as non-negative integers
+// (the engine rejects negative ones at construction). The candidate
+// saturates at 0xFFFFFFFE: a finite distance never becomes INF_LABEL and
+// never wraps. These kernels sit next to the hop/CC ones, which stay as
+// they are: a vertex's label can improve in several iterations here, so
+// neither the visited bitmap nor a settled-row skip applies.
+
+__device__ __forceinline__ uint32_t sat_add_label(uint32_t lab, uint32_t w) {
+  unsigned long long c = (unsigned long long)lab + w;
+  return c > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)c;
+}
+
+// Push CSR with the weight riding next to its dst: one interleaved
+// {global dst, weight} per out-edge at the claimed cursor position, so the
+// two can never drift apart under the non-deterministic cursor order and
+// the scatter fetches an edge with one coalesced 8-byte load per lane.
+__global__ void csr_scatter_w_kernel(uint64_t ep, const V_ID* col,
+                                     const WeightType* weight,
+                                     const E_ID* row_ptr_loc, V_ID vp,
+                                     V_ID row_left,
+                                     unsigned long long* cursor,
+                                     uint2* push_edge) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < ep;
+       j += stride) {
+    V_ID lo = 0, hi = vp - 1;
+    while (lo < hi) {
+      V_ID mid = (lo + hi + 1) >> 1;
+      if (row_ptr_loc[mid] <= j) lo = mid;
+      else hi = mid - 1;
+    }
+    V_ID src = col[j];
+    unsigned long long pos = atomicAdd(&cursor[src], 1ull);
+    push_edge[pos] = make_uint2(lo + row_left, (uint32_t)weight[j]);
+  }
+}
+
+// push_chunk_scatter_kernel's min-plus twin: same work items, chunking,
+// grid-stride over the device-side count and the same two output shapes,
+// but every edge carries its own candidate sat(old_labels[u] + w).
+template <bool NEW_DENSE>
+__global__ void push_chunk_scatter_w_kernel(
+    const uint2* items, const uint32_t* counter, uint32_t max_items,
+    const E_ID* push_row_ptr, const uint2* push_edge,
+    const uint32_t* old_labels, const uint32_t* snapshot,
+    uint32_t* new_labels, V_ID my_row_left, uint8_t* new_seg,
+    V_ID capacity) {
+  __shared__ uint32_t lds_scan[BLOCK / WAVE + 1];
+  __shared__ uint32_t queue_base;
+  V_ID* new_queue = nullptr;
+  uint32_t* num_nodes = nullptr;
+  if (!NEW_DENSE) {
+    num_nodes = &((FrontierHeader*)new_seg)->numNodes;
+    new_queue = (V_ID*)(new_seg + sizeof(FrontierHeader));
+  }
+  uint32_t n = *counter;
+  if (n > max_items) n = max_items;
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    uint2 it = items[i];
+    V_ID u = it.x;
+    uint32_t src_lab = old_labels[u];  // start-of-iteration value (Jacobi)
+    E_ID b = push_row_ptr[u] + (E_ID)it.y * PUSH_CHUNK;
+    E_ID e = push_row_ptr[u + 1];
+    if (e > b + PUSH_CHUNK) e = b + PUSH_CHUNK;
+    uint32_t nstripes =
+        (uint32_t)((e - b + blockDim.x - 1) / blockDim.x);
+    if (NEW_DENSE) {
+      // 4 stripes per pass: 4 edge loads, then 4 dependent label-line
+      // reads in flight (as in the hop kernel's dense path)
+      uint32_t s = 0;
+      for (; s + 4 <= nstripes; s += 4) {
+        E_ID k0 = b + (E_ID)s * blockDim.x + threadIdx.x;
+        uint2 e0 = make_uint2(0, 0), e1 = e0, e2 = e0, e3 = e0;
+        bool p0 = k0 < e, p1 = k0 + blockDim.x < e,
+             p2 = k0 + 2 * blockDim.x < e, p3 = k0 + 3 * blockDim.x < e;
+        if (p0) e0 = push_edge[k0];
+        if (p1) e1 = push_edge[k0 + blockDim.x];
+        if (p2) e2 = push_edge[k0 + 2 * blockDim.x];
+        if (p3) e3 = push_edge[k0 + 3 * blockDim.x];
+#define LUX_PDW_EDGE(P_, E_)                                                \
+        if (P_) {                                                           \
+          uint32_t cand = sat_add_label(src_lab, (E_).y);                   \
+          uint32_t* slot = &new_labels[(E_).x - my_row_left];               \
+          uint32_t cur = __hip_atomic_load(slot, __ATOMIC_RELAXED,          \
+                                           __HIP_MEMORY_SCOPE_AGENT);       \
+          if (cand < cur) atomicMin(slot, cand);                            \
+        }
+        LUX_PDW_EDGE(p0, e0)
+        LUX_PDW_EDGE(p1, e1)
+        LUX_PDW_EDGE(p2, e2)
+        LUX_PDW_EDGE(p3, e3)
+      }
+      for (; s < nstripes; s++) {
+        E_ID k = b + (E_ID)s * blockDim.x + threadIdx.x;
+        if (k < e) {
+          uint2 ed = push_edge[k];
+          LUX_PDW_EDGE(true, ed)
+        }
+      }
+#undef LUX_PDW_EDGE
+      continue;
+    }
+    for (uint32_t s = 0; s < nstripes; s++) {
+      E_ID k = b + (E_ID)s * blockDim.x + threadIdx.x;
+      uint32_t flag = 0;
+      V_ID dstv = 0;
+      if (k < e) {
+        uint2 ed = push_edge[k];
+        V_ID lv = ed.x - my_row_left;
+        uint32_t cand = sat_add_label(src_lab, ed.y);
+        uint32_t* slot = &new_labels[lv];
+        uint32_t cur = __hip_atomic_load(slot, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+        if (cand < cur) {
+          // first-improvement enqueue: labels only fall below the
+          // snapshot, so exactly one atomicMin per improved vertex and
+          // iteration returns the snapshot value
+          uint32_t last = snapshot[lv];
+          uint32_t act = atomicMin(slot, cand);
+          if (act == last) {
+            flag = 1;
+            dstv = ed.x;
+          }
+        }
+      }
+      __syncthreads();
+      uint32_t q_total;
+      uint32_t q_off = block_exscan<uint32_t, BLOCK>(flag, lds_scan,
+                                                     &q_total);
+      if (threadIdx.x == 0 && q_total)
+        queue_base = atomicAdd(num_nodes, q_total);
+      __syncthreads();
+      if (flag) {
+        uint32_t pos = queue_base + q_off;
+        if (pos < capacity) new_queue[pos] = dstv;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Weighted check oracle over my pull-CSC partition: edges with
+// label[v] > sat(label[u] + w) for a finite label[u], plus one if the
+// source (counted by the rank that owns it) is not at distance 0.
+__global__ void check_w_kernel(V_ID vp, V_ID row_left,
+                               const E_ID* row_ptr_loc, const V_ID* col,
+                               const WeightType* weight,
+                               const uint32_t* labels, V_ID source,
+                               unsigned long long* mistakes) {
+  __shared__ unsigned long long lds[BLOCK / WAVE];
+  unsigned long long cnt = 0;
+  for (V_ID v = blockIdx.x * blockDim.x + threadIdx.x; v < vp;
+       v += blockDim.x * gridDim.x) {
+    uint32_t lab = labels[row_left + v];
+    if (row_left + v == source && lab != 0) cnt++;
+    for (E_ID j = row_ptr_loc[v]; j < row_ptr_loc[v + 1]; j++) {
+      uint32_t sl = labels[col[j]];
+      if (sl != INF_LABEL && lab > sat_add_label(sl, (uint32_t)weight[j]))
+        cnt++;
+    }
+  }
+  cnt = block_reduce_sum(cnt, lds);
+  if (threadIdx.x == 0 && cnt) atomicAdd(mistakes, cnt);
+}
+
 }  // namespace lux
 
 // ---------------- C ABI ----------------
@@ -738,6 +904,56 @@ void lux_gpu_check(uint64_t stream, int is_min, V_ID vp, V_ID row_left,
     hipLaunchKernelGGL(check_kernel<false>, dim3(grid_for(vp)), dim3(BLOCK),
                        0, s, vp, row_left, row_ptr_loc, col, labels,
                        mistakes);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ---- weighted SSSP (min-plus) ----
+
+// push_edge: uint2[ep] {global dst, weight}; cursor as lux_gpu_csr_scatter
+void lux_gpu_csr_scatter_w(uint64_t stream, uint64_t ep, const V_ID* col,
+                           const WeightType* weight, const E_ID* row_ptr_loc,
+                           V_ID vp, V_ID row_left,
+                           unsigned long long* cursor, uint2* push_edge) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ep == 0 || vp == 0) return;
+  hipLaunchKernelGGL(csr_scatter_w_kernel, dim3(grid_for(ep)), dim3(BLOCK), 0,
+                     s, ep, col, weight, row_ptr_loc, vp, row_left, cursor,
+                     push_edge);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_push_chunk_scatter_w(uint64_t stream, int new_dense,
+                                  const uint2* items, const uint32_t* counter,
+                                  uint32_t max_items,
+                                  const E_ID* push_row_ptr,
+                                  const uint2* push_edge,
+                                  const uint32_t* old_labels,
+                                  const uint32_t* snapshot,
+                                  uint32_t* new_labels, V_ID my_row_left,
+                                  uint8_t* new_seg, V_ID capacity) {
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(MAX_GRID), blk(BLOCK);
+  if (new_dense)
+    hipLaunchKernelGGL(push_chunk_scatter_w_kernel<true>, grid, blk, 0, s,
+                       items, counter, max_items, push_row_ptr, push_edge,
+                       old_labels, snapshot, new_labels, my_row_left, new_seg,
+                       capacity);
+  else
+    hipLaunchKernelGGL(push_chunk_scatter_w_kernel<false>, grid, blk, 0, s,
+                       items, counter, max_items, push_row_ptr, push_edge,
+                       old_labels, snapshot, new_labels, my_row_left, new_seg,
+                       capacity);
+  LUX_POST_LAUNCH(stream);
+}
+
+void lux_gpu_check_w(uint64_t stream, V_ID vp, V_ID row_left,
+                     const E_ID* row_ptr_loc, const V_ID* col,
+                     const WeightType* weight, const uint32_t* labels,
+                     V_ID source, unsigned long long* mistakes) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(check_w_kernel, dim3(grid_for(vp)), dim3(BLOCK), 0, s,
+                     vp, row_left, row_ptr_loc, col, weight, labels, source,
+                     mistakes);
   LUX_POST_LAUNCH(stream);
 }
 

@@ -68,6 +68,19 @@ void lux_gpu_blocked_scatter(uint64_t stream, uint64_t ep,
                              const lux::V_ID* bounds, int nb, lux::V_ID lo,
                              lux::V_ID hi, unsigned long long* cursor,
                              lux::V_ID* out_col);
+// weighted SSSP: blocked scatter moving col and its weight to one slot;
+// endpoint-hash weights for synthetic graphs
+void lux_gpu_blocked_scatter_w(uint64_t stream, uint64_t ep,
+                               const lux::V_ID* col,
+                               const lux::WeightType* weight,
+                               const lux::E_ID* row_ptr_loc, lux::V_ID vp,
+                               const lux::V_ID* bounds, int nb, lux::V_ID lo,
+                               lux::V_ID hi, unsigned long long* cursor,
+                               lux::V_ID* out_col, lux::WeightType* out_w);
+void lux_gpu_hash_weights(uint64_t stream, uint64_t ep, const lux::V_ID* col,
+                          const lux::E_ID* row_ptr_loc, lux::V_ID vp,
+                          lux::V_ID row_left, uint64_t seed, uint32_t wmax,
+                          lux::WeightType* weight);
 
 // pull.hip
 void lux_gpu_build_bins(uint64_t stream, uint32_t vp,
@@ -82,6 +95,14 @@ void lux_gpu_pull_iter(uint64_t stream, int mode, uint32_t n0,
                        int row_u32, const lux::V_ID* col, const void* oldv,
                        void* newv, const lux::V_ID* deg, lux::V_ID row_left,
                        float init_rank);
+// weighted SSSP dense sweep (min-plus, saturating; wgt indexed like col)
+void lux_gpu_pull_iter_w(uint64_t stream, uint32_t n0, const lux::V_ID* bin0,
+                         uint32_t n1, const lux::V_ID* bin1, uint32_t n2,
+                         const lux_uint2* bin2, uint32_t nbig,
+                         const lux::V_ID* bin2v, const void* row_ptr,
+                         int row_u32, const lux::V_ID* col,
+                         const lux::WeightType* wgt, const uint32_t* oldv,
+                         uint32_t* newv, lux::V_ID row_left);
 void lux_gpu_pull_finish_pr(uint64_t stream, lux::V_ID vp, float* newv,
                             const lux::V_ID* deg, lux::V_ID row_left,
                             float init_rank);
@@ -189,6 +210,26 @@ void lux_gpu_check(uint64_t stream, int is_min, lux::V_ID vp,
                    lux::V_ID row_left, const lux::E_ID* row_ptr_loc,
                    const lux::V_ID* col, const uint32_t* labels,
                    unsigned long long* mistakes);
+// weighted SSSP (min-plus): push CSR of interleaved {dst, weight} edges,
+// per-edge-candidate chunk scatter, weighted check oracle
+void lux_gpu_csr_scatter_w(uint64_t stream, uint64_t ep, const lux::V_ID* col,
+                           const lux::WeightType* weight,
+                           const lux::E_ID* row_ptr_loc, lux::V_ID vp,
+                           lux::V_ID row_left, unsigned long long* cursor,
+                           lux_uint2* push_edge);
+void lux_gpu_push_chunk_scatter_w(uint64_t stream, int new_dense,
+                                  const lux_uint2* items,
+                                  const uint32_t* counter, uint32_t max_items,
+                                  const lux::E_ID* push_row_ptr,
+                                  const lux_uint2* push_edge,
+                                  const uint32_t* old_labels,
+                                  const uint32_t* snapshot,
+                                  uint32_t* new_labels, lux::V_ID my_row_left,
+                                  uint8_t* new_seg, lux::V_ID capacity);
+void lux_gpu_check_w(uint64_t stream, lux::V_ID vp, lux::V_ID row_left,
+                     const lux::E_ID* row_ptr_loc, const lux::V_ID* col,
+                     const lux::WeightType* weight, const uint32_t* labels,
+                     lux::V_ID source, unsigned long long* mistakes);
 
 // cf.hip
 void lux_gpu_cf_seed(uint64_t stream, uint64_t n, const float* oldv,

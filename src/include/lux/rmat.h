@@ -81,6 +81,17 @@ LUX_HD WeightType rmat_weight(uint64_t seed, uint64_t e) {
   return (WeightType)(splitmix64(seed ^ 0xABCD1234u ^ (e * 0x2545F4914F6CDD1Dull)) % 5) + 1;
 }
 
+// Deterministic edge weight for weighted synthetic graphs (SSSP): int in
+// [1, wmax], a pure function of the edge's endpoints — the full, sliced,
+// CPU and GPU builds agree without the generators knowing about weights
+// (parallel edges share a weight).
+LUX_HD WeightType edge_hash_weight(uint64_t seed, V_ID src, V_ID dst,
+                                   uint32_t wmax) {
+  uint64_t key = ((uint64_t)src << 32) | dst;
+  return (WeightType)(1 + splitmix64(seed ^ 0x5757575757575757ull ^ key) %
+                              wmax);
+}
+
 // Bipartite synthetic generator for CF (NetFlix-shaped: users x items).
 // Edge pair 2r/2r+1 stores rating r in BOTH directions (user <-> item),
 // matching the reference's NetFlix file whose 200.9M edges are 100.5M
