@@ -238,6 +238,25 @@ def check_w(stream, vp, row_left, row_ptr_loc, col, weight, labels, source,
                           _u32(source), dp(mistakes))
 
 
+def bucket_select(stream, vp, snapshot, labels_part, dirty, limit, replace,
+                  seg, meta):
+    """Bucketed-schedule select pass (push.hip bucket_select_kernel). The
+    kernel stores whole u64 words: dirty needs 2 * ceil(vp / 64) u32 words
+    and seg 8 + 8 * ceil(vp / 64) bytes, checked here because a short
+    buffer would be written past its end."""
+    words = (int(vp) + 63) // 64
+    if not isinstance(dirty, int) and dirty is not None:
+        assert dirty.numel() * dirty.element_size() >= 8 * words, \
+            "bucket_select: dirty shorter than 2 * ceil(vp / 64) u32 words"
+    if not isinstance(seg, int) and seg is not None:
+        assert seg.numel() * seg.element_size() >= 8 + 8 * words, \
+            "bucket_select: seg shorter than 8 + 8 * ceil(vp / 64) bytes"
+    lib().lux_gpu_bucket_select(_u64(stream), _u32(vp), dp(snapshot),
+                                dp(labels_part), dp(dirty), dp(limit),
+                                ctypes.c_int(int(bool(replace))), dp(seg),
+                                dp(meta))
+
+
 def pull_finish_pr(stream, vp, newv, deg, row_left, init_rank):
     lib().lux_gpu_pull_finish_pr(_u64(stream), _u32(vp), dp(newv), dp(deg),
                                  _u32(row_left), ctypes.c_float(init_rank))

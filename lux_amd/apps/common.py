@@ -28,6 +28,8 @@ class AppArgs:
         self.synthetic = None  # e.g. "rmat:20:1000000"
         self.weighted = False  # sssp: min-plus over the edge weights
         self.wmax = 16  # sssp -weighted -synthetic: hash weights in [1, wmax]
+        self.delta = 0  # sssp -weighted: bucket width of the bucketed
+        #                 (near-far delta-stepping) schedule; 0 = off
 
 
 def parse_input_args(argv):
@@ -61,6 +63,8 @@ def parse_input_args(argv):
             a.weighted = True; i += 1
         elif f == "-wmax":
             a.wmax = int(argv[i + 1]); i += 2
+        elif f == "-delta":
+            a.delta = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

@@ -1,7 +1,8 @@
 """SSSP app driver (reference parity: sssp/sssp.cc; unweighted hop
 distances, push model with adaptive frontiers). -weighted runs min-plus
 relaxation over the graph's edge weights instead (-file: the .lux weights;
--synthetic rmat/rmat_folded: endpoint-hash weights in [1, -wmax])."""
+-synthetic rmat/rmat_folded: endpoint-hash weights in [1, -wmax]);
+-delta D (with -weighted) runs it on the bucketed schedule of width D."""
 import sys
 
 from .. import dist as dx
@@ -38,6 +39,9 @@ def build_sssp_bench(args, device):
 
 def main(argv=None):
     a = parse_input_args(sys.argv[1:] if argv is None else argv)
+    if a.delta < 0 or (a.delta and not a.weighted):
+        raise SystemExit("-delta D needs D >= 0 and -weighted (the bucketed "
+                         "schedule orders vertices by weighted distance)")
     dx.init_process_group("cuda")
     import torch
     local = dx.env_local_rank()
@@ -51,11 +55,13 @@ def main(argv=None):
         print_memory_estimate(part.nv, part.ne, dx.world_size(),
                               weighted=a.weighted)
     eng = PushEngine(part, PushEngine.MODE_MIN, source=a.start,
-                     weighted=a.weighted)
+                     weighted=a.weighted, delta=a.delta)
     with ElapsedTimer():
         iters = eng.run()
     if dx.rank() == 0:
-        print(f"[lux] converged in {iters} iterations")
+        adv = f" and {eng.bucket_advances} bucket advances" if a.delta \
+            else ""
+        print(f"[lux] converged in {iters} iterations{adv}")
     if a.verbose and dx.rank() == 0 and hasattr(eng, "stats"):
         from ..trace import IterTrace
         tr = IterTrace()

@@ -37,6 +37,8 @@ from .types import (DENSE_BITMAP, SPARSE_QUEUE, frontier_bytes,
                     frontier_capacity)
 
 U8, U32, U64 = torch.uint8, torch.int32, torch.int64
+INF_LABEL = 0xFFFFFFFF
+SAT_LABEL = 0xFFFFFFFE  # largest finite label (push.hip sat_add_label)
 
 
 def _stream():
@@ -88,13 +90,25 @@ class PushEngine:
     MODE_MIN = 1  # SSSP
     MODE_MAX = 2  # CC
 
-    def __init__(self, part: GraphPart, mode, source=0, weighted=False):
+    def __init__(self, part: GraphPart, mode, source=0, weighted=False,
+                 delta=None):
         """weighted (MODE_MIN only): min-plus relaxation over part.weight
         (non-negative i32; ValueError on a negative one, agreed across
         ranks). Labels are exact shortest distances, saturating at
         0xFFFFFFFE; unreachable vertices keep INF. A label can improve in
         several iterations, so this mode uses neither the visited bitmap
-        nor the pull kernels' settled-row skip."""
+        nor the pull kernels' settled-row skip.
+
+        delta (weighted only; None or 0 = off): bucketed near-far schedule
+        with bucket width delta. Only dirty vertices with label <= limit
+        relax; the rest wait in a dirty bitmap until the limit advances to
+        their bucket (see the "bucketed schedule" section below). Same
+        labels, fewer relaxed edges, more iterations."""
+        if delta is not None and delta < 0:
+            raise ValueError("delta must be >= 0")
+        if delta and not weighted:
+            raise ValueError("delta (bucketed schedule) needs weighted=True")
+        self.delta = int(delta or 0)
         self.part = part
         self.mode = mode
         self.is_min = mode == self.MODE_MIN
@@ -211,6 +225,19 @@ class PushEngine:
         self._graphs = {}
         self._graph_uses = {}
         self._fq_init = None
+        self.bucket_advances = 0
+        self._seed_vols = {}
+        if self.delta:
+            # deferred set: one bit per local vertex, whole u64 words
+            # (bucket_select stores them wave by wave)
+            self.dirty = torch.zeros(2 * max((p.vp + 63) // 64, 1),
+                                     dtype=U32, device=device)
+            # device-resident limit: captured bodies replay across buckets
+            self._limit_dev = torch.zeros(1, dtype=U32, device=device)
+            # per-iteration preset of meta[6..7] (min deferred label,
+            # deferred count), copied D2D like _hdr_zero
+            self._meta67_init = torch.tensor([-1, 0], dtype=U32,
+                                             device=device)
         self.reset(source)
 
     def reset(self, source=None):
@@ -266,6 +293,14 @@ class PushEngine:
         self.iterations = 0
         self.stats = []
         self._bits_stale = True
+        self.bucket_advances = 0
+        if self.delta:
+            # the seed is the active set (it sits in the segment); nothing
+            # is deferred; snapshot == labels_part is the standing invariant
+            self.dirty.zero_()
+            self.snapshot.copy_(self.labels_part)
+            self.meta_host[:, 6] = INF_LABEL
+            self._set_limit(min(self.delta - 1, SAT_LABEL))
 
     # -------- helpers --------
     def _my_seg_i32(self):
@@ -348,8 +383,12 @@ class PushEngine:
                                   self.labels.narrow(0, p.row_left, p.vp))
 
     def _run_single_body(self, pull, new_dense):
-        import os
         key = ("pull",) if pull else ("push", bool(new_dense))
+        self._run_captured(key,
+                           lambda: self._single_body(pull, new_dense))
+
+    def _run_captured(self, key, body):
+        import os
         g = self._graphs.get(key)
         if g is not None:
             g.replay()
@@ -362,7 +401,7 @@ class PushEngine:
                 torch.cuda.synchronize()
                 cg = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(cg):
-                    self._single_body(pull, new_dense)
+                    body()
                 self._graphs[key] = cg
                 cg.replay()  # capture records, doesn't run
                 return
@@ -370,7 +409,7 @@ class PushEngine:
                 print(f"[lux] push hipGraph capture disabled: {e}")
                 os.environ["LUX_HIPGRAPH"] = "0"
                 torch.cuda.synchronize()
-        self._single_body(pull, new_dense)
+        body()
 
     def _step_single(self):
         """World-1 fast path: replay the captured iteration graph, then
@@ -428,7 +467,10 @@ class PushEngine:
         nparts = p.nparts
         ws = dx.world_size()
         if ws == 1 and nparts == 1:
-            return self._step_single()
+            return self._step_single_bucketed() if self.delta \
+                else self._step_single()
+        if self.delta:
+            return self._step_multi_bucketed()
         mh = self.meta_host  # (nparts, 8) u32 describing CURRENT frontier
         types = mh[:, 0]
         counts = mh[:, 1]
@@ -481,27 +523,7 @@ class PushEngine:
             # (possibly stale) replicated labels from it before the
             # scatter reads them
             self.item_counter.zero_()
-            # repair even at ws==1: sparse iterations skip the label
-            # publish, so the replicated array is stale for exactly the
-            # queued vertices — the annex carries their fresh labels
-            repair = self.labels
-            for q in range(nparts):
-                typ, num = int(types[q]), int(counts[q])
-                if p.verts_all[q] == 0:
-                    continue
-                seg = self.fq_all.narrow(0, int(self.seg_off[q]),
-                                         self.seg_bytes[q])
-                if typ == DENSE_BITMAP:
-                    ng.frontier_expand(s, 1, p.row_left_all[q],
-                                       p.verts_all[q], seg, None, None,
-                                       self.push_row_ptr, self.items,
-                                       self.item_counter, self.max_items)
-                elif num:
-                    annex = self.fq_annex_all.narrow(
-                        0, int(self.annex_off[q]), num)
-                    ng.frontier_expand(s, 0, 0, num, seg, annex, repair,
-                                       self.push_row_ptr, self.items,
-                                       self.item_counter, self.max_items)
+            self._expand_segments(s, types, counts)
             bits = None
             if self.visited is not None and p.vp > 0:
                 if self._bits_stale:
@@ -522,35 +544,9 @@ class PushEngine:
                           self.tmp_seg, self.meta_mine, item_counter,
                           self.max_items)
 
-        # ---- exchange: meta first (the ONE host read), then payloads ----
-        dx.all_gather_slices(self.meta_all, self.meta_mine,
-                             [8] * nparts, [8 * q for q in range(nparts)],
-                             my_index=p.p)
-        mh = self.meta_all.cpu().numpy().view(np.uint32).reshape(nparts, 8)
-        self.meta_host = mh
+        mh = self._exchange()
         ntypes, ncounts = mh[:, 0], mh[:, 1]
-
-        # payload exchange from the fresh meta: only USED bytes travel
         me = p.p
-        h, lab_n = exchange_frontier_payloads(
-            mh, p.verts_all, self.fq_all, self.new_seg,
-            [int(o) for o in self.seg_off[:-1]], self.fq_annex_all,
-            self.new_annex, [int(o) for o in self.annex_off[:-1]],
-            self.labels, self.labels_part, p.row_left_all, me)
-        h.wait()
-        # slice q is fresh iff q published it now, or it was fresh before
-        # and q changed nothing this iteration
-        if self.labels_current:
-            self.labels_current = all(
-                lab_n[q] > 0 or ncounts[q] == 0 or p.verts_all[q] == 0
-                for q in range(nparts))
-        else:
-            self.labels_current = all(
-                lab_n[q] > 0 or p.verts_all[q] == 0
-                for q in range(nparts))
-
-        self.headers = [(int(ntypes[q]), int(ncounts[q]))
-                        for q in range(nparts)]
         self.iterations += 1
         # per-iteration trace row (reference -verbose parity,
         # sssp_gpu.cu:516-518: activeNodes + phase info per partition)
@@ -562,12 +558,264 @@ class PushEngine:
                                my_new=my_new))
         return int(ncounts.sum())
 
+    def _expand_segments(self, s, types, counts):
+        """Expand every source segment into work items (item_counter is
+        zeroed by the caller)."""
+        p = self.part
+        # repair even at ws==1: sparse iterations skip the label
+        # publish, so the replicated array is stale for exactly the
+        # queued vertices — the annex carries their fresh labels
+        repair = self.labels
+        for q in range(p.nparts):
+            typ, num = int(types[q]), int(counts[q])
+            if p.verts_all[q] == 0:
+                continue
+            seg = self.fq_all.narrow(0, int(self.seg_off[q]),
+                                     self.seg_bytes[q])
+            if typ == DENSE_BITMAP:
+                ng.frontier_expand(s, 1, p.row_left_all[q],
+                                   p.verts_all[q], seg, None, None,
+                                   self.push_row_ptr, self.items,
+                                   self.item_counter, self.max_items)
+            elif num:
+                annex = self.fq_annex_all.narrow(
+                    0, int(self.annex_off[q]), num)
+                ng.frontier_expand(s, 0, 0, num, seg, annex, repair,
+                                   self.push_row_ptr, self.items,
+                                   self.item_counter, self.max_items)
+
+    def _exchange(self):
+        """Meta first (the ONE host read), then the payloads it sizes.
+        Updates meta_host, headers and label freshness; returns the meta
+        table."""
+        p = self.part
+        nparts = p.nparts
+        dx.all_gather_slices(self.meta_all, self.meta_mine,
+                             [8] * nparts, [8 * q for q in range(nparts)],
+                             my_index=p.p)
+        mh = self.meta_all.cpu().numpy().view(np.uint32).reshape(nparts, 8)
+        self.meta_host = mh
+        ntypes, ncounts = mh[:, 0], mh[:, 1]
+
+        # payload exchange from the fresh meta: only USED bytes travel
+        me = p.p
+        h, _ = exchange_frontier_payloads(
+            mh, p.verts_all, self.fq_all, self.new_seg,
+            [int(o) for o in self.seg_off[:-1]], self.fq_annex_all,
+            self.new_annex, [int(o) for o in self.annex_off[:-1]],
+            self.labels, self.labels_part, p.row_left_all, me)
+        h.wait()
+        # slice q is fresh iff q published it now, or it was fresh before
+        # and q changed nothing this iteration. Bucketed: a rank can change
+        # labels and defer them all (new count 0), so only a published
+        # slice counts; _sync_labels() before a pull does the catch-up
+        self.labels_current = self._labels_fresh(self.labels_current, mh)
+
+        self.headers = [(int(ntypes[q]), int(ncounts[q]))
+                        for q in range(nparts)]
+        return mh
+
+    def _labels_fresh(self, was_fresh, mh):
+        """Are all replicated label slices fresh after the exchange that
+        meta table `mh` sized? Dense ranks published theirs."""
+        p = self.part
+        for q in range(p.nparts):
+            if p.verts_all[q] == 0 or int(mh[q, 0]) == DENSE_BITMAP:
+                continue
+            if self.delta or not was_fresh or int(mh[q, 1]) != 0:
+                return False
+        return True
+
+    # -------- bucketed schedule (near-far delta-stepping) --------
+    # State: labels; `dirty`, the bitmap of vertices that improved since
+    # they last relaxed their out-edges and lie beyond the limit (the
+    # deferred set — the near ones are the active set and sit in the
+    # frontier segment, so nothing is ever queued twice); `limit`, a global
+    # u32 (near <=> label <= limit), device-resident so captured bodies
+    # replay across buckets.
+    #   relax   push: out-edges of the active set A, then
+    #                 dirty = (dirty \ A) | changed
+    #           pull: every edge (the plain rule applied to A), then
+    #                 dirty = changed
+    #   select  ng.bucket_select splits dirty into the next A (dense
+    #           bitmap, finished by frontier_fixup(built_dense=1) as usual)
+    #           and the deferred rest; meta[6] = min deferred label,
+    #           meta[7] = deferred count
+    #   advance A empty, deferred not: limit jumps to the end of the bucket
+    #           holding the global min deferred label, select again. No
+    #           edge is relaxed; counted in bucket_advances, not iterations
+    # snapshot == labels_part holds between iterations: select refreshes
+    # the snapshot where it saw a change, replacing the per-iteration copy.
+
+    def _set_limit(self, limit):
+        self.limit = int(limit)
+        # U32 buffers are torch.int32: pass the same 32 bits
+        self._limit_dev.fill_(self.limit - (1 << 32)
+                              if self.limit >= 1 << 31 else self.limit)
+
+    def _seed_volume(self):
+        """Global out-degree of the source (stats only: the decision leaves
+        the seed unpriced). Read once per source."""
+        p = self.part
+        cache = self._seed_vols
+        if self.source not in cache:
+            mine = p.vp > 0 and p.row_left <= self.source <= p.row_right
+            v = self.deg_part.narrow(0, self.source - p.row_left, 1).to(U64) \
+                if mine else torch.zeros(1, dtype=U64, device=self.device)
+            dx.all_reduce_sum_(v)
+            cache[self.source] = int(v.item()) & 0xFFFFFFFF
+        return cache[self.source]
+
+    def _bucket_decide(self):
+        """(active count, its out-edge volume, overflow, pull) from the
+        meta table of the current active set — the plain engine's rule."""
+        import os
+        p = self.part
+        mh = self.meta_host
+        evol = int((mh[:, 2].astype(np.uint64)
+                    | (mh[:, 3].astype(np.uint64) << np.uint64(32))).sum())
+        overflow = bool(mh[:, 4].any())
+        active = int(mh[:, 1].sum())
+        pull = overflow or active > p.nv // 16
+        if overflow:
+            print("[lux] frontier expand overflow: recovering with a "
+                  "forced pull iteration", file=sys.stderr)
+        if not pull:
+            div = int(os.environ.get("LUX_PUSH_EVOL_DIV", "0") or 0)
+            pull = evol > (p.ne // div if div else p.ne // 8)
+        return active, evol, overflow, pull
+
+    def needs_advance(self):
+        """No near vertex left but deferred ones are (and no overflow
+        pending: the forced pull comes first)."""
+        mh = self.meta_host
+        return bool(self.delta) and int(mh[:, 1].sum()) == 0 \
+            and int(mh[:, 7].sum()) > 0 and not mh[:, 4].any()
+
+    def _bucket_row(self, active, evol, pull, limit):
+        mh = self.meta_host
+        me = self.part.p if mh.shape[0] > 1 else 0
+        if self.iterations == 1:
+            evol = self._seed_volume()
+        self.stats.append(dict(iter=self.iterations, old_frontier=active,
+                               pull_fallback=bool(pull),
+                               out_dense=bool(mh[me, 0] == DENSE_BITMAP),
+                               my_new=int(mh[me, 1]), limit=limit,
+                               volume=evol,
+                               deferred=int(mh[:, 7].sum())))
+
+    def _bucket_prologue(self):
+        """Capturable per-iteration presets: zero my new header, reset the
+        deferred min / count words of the meta record."""
+        self.new_seg[:8].copy_(self._hdr_zero)
+        self.meta_mine[6:8].copy_(self._meta67_init)
+
+    def _bucket_select_fixup(self, s, replace, counter):
+        p = self.part
+        ng.bucket_select(s, p.vp, self.snapshot, self.labels_part,
+                         self.dirty, self._limit_dev, replace, self.new_seg,
+                         self.meta_mine)
+        ng.frontier_fixup(s, p.vp, p.row_left, self.capacity, 1,
+                          self.snapshot, self.labels_part, self.deg_part,
+                          self.new_seg, self.new_annex, self.tmp_seg,
+                          self.meta_mine, counter, self.max_items)
+
+    def _bucket_body(self, kind):
+        """World-1 bucketed body, kind = "pull" | "push" | "select" (the
+        advance's reselect). Static shapes and addresses: capturable."""
+        p = self.part
+        s = _stream()
+        self._bucket_prologue()
+        counter = None
+        if kind == "pull":
+            run_pull(p, self._pull_mode, self.labels, self.labels_part,
+                     None, 0.0)
+        elif kind == "push":
+            self.item_counter.zero_()
+            ng.frontier_expand_auto(s, p.vp, p.row_left, self.fq_all,
+                                    self.fq_annex_all, self.labels,
+                                    self.push_row_ptr, self.items,
+                                    self.item_counter, self.max_items)
+            self._scatter(s, True, None)  # label atomics only, no enqueue
+            counter = self.item_counter
+        self._bucket_select_fixup(s, kind == "pull", counter)
+        self.fq_all.copy_(self.new_seg)
+        self.fq_annex_all[:self.capacity].copy_(self.new_annex)
+        ng.publish_labels_guarded(s, p.vp, self.meta_mine,
+                                  self.labels_part,
+                                  self.labels.narrow(0, p.row_left, p.vp))
+
+    def _run_bucket_single(self, kind):
+        self._run_captured(("bucket", kind),
+                           lambda: self._bucket_body(kind))
+        mh = self.meta_mine.cpu().numpy().view(np.uint32).reshape(1, 8)
+        self.meta_host = mh
+        self.labels_current = int(mh[0, 0]) == DENSE_BITMAP
+        self.headers = [(int(mh[0, 0]), int(mh[0, 1]))]
+
+    def advance(self):
+        """Bucket advance: move the limit to the end of the bucket that
+        holds the global minimum deferred label and select again (select +
+        fixup + the usual exchange, no relaxation). Every rank computes
+        the same limit from the exchanged meta table."""
+        p = self.part
+        m = int(self.meta_host[:, 6].min())
+        self._set_limit(min((m // self.delta + 1) * self.delta - 1,
+                            SAT_LABEL))
+        self.bucket_advances += 1
+        if dx.world_size() == 1 and p.nparts == 1:
+            self._run_bucket_single("select")
+            return
+        self._bucket_prologue()
+        self._bucket_select_fixup(_stream(), False, None)
+        self._exchange()
+
+    def _step_single_bucketed(self):
+        p = self.part
+        if self.needs_advance():
+            self.advance()
+        active, evol, _, pull = self._bucket_decide()
+        limit = self.limit
+        if pull and not self.labels_current:
+            self.labels.narrow(0, p.row_left, p.vp).copy_(self.labels_part)
+            self.labels_current = True
+        self._run_bucket_single("pull" if pull else "push")
+        self.iterations += 1
+        self._bucket_row(active, evol, pull, limit)
+        return int(self.meta_host[0, 1])
+
+    def _step_multi_bucketed(self):
+        p = self.part
+        s = _stream()
+        if self.needs_advance():
+            self.advance()
+        mh = self.meta_host
+        active, evol, _, pull = self._bucket_decide()
+        limit = self.limit
+        self._bucket_prologue()
+        if pull:
+            self._sync_labels()  # pull reads every vertex's label
+            run_pull(p, self._pull_mode, self.labels, self.labels_part,
+                     None, 0.0)
+            counter = None
+        else:
+            self.item_counter.zero_()
+            self._expand_segments(s, mh[:, 0], mh[:, 1])
+            self._scatter(s, True, None)
+            counter = self.item_counter
+        self._bucket_select_fixup(s, pull, counter)
+        mh = self._exchange()
+        self.iterations += 1
+        self._bucket_row(active, evol, pull, limit)
+        return int(mh[:, 1].sum())
+
     def run(self, max_iters=None):
         """Iterate to convergence (every partition reports an empty new
-        frontier)."""
+        frontier; bucketed: and an empty deferred set)."""
         while True:
             total = self.step()
-            if total == 0 and not self.meta_host[:, 4].any():
+            if total == 0 and not self.meta_host[:, 4].any() \
+                    and not (self.delta and self.meta_host[:, 7].any()):
                 break  # overflow never terminates: forced pull recovers
             if max_iters and self.iterations >= max_iters:
                 break

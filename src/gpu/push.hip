@@ -426,7 +426,9 @@ __global__ void d2s_kernel(V_ID vp, V_ID row_left, const uint8_t* dense_seg,
 // volume of the new frontier (global out-degrees of its vertices — the
 // engine's exact push-vs-pull input for the NEXT iteration) [4]=expand
 // overflow flag [5]=fixup flag scratch (1=convert d2s, 2=rebuild dense)
-// [6..7]=pad.
+// [6..7]=pad; the bucketed schedule keeps the minimum deferred label and
+// the deferred count there (bucket_select_kernel) — nothing in this chain
+// touches them.
 
 __global__ void fixup_decide_kernel(int built_dense, V_ID capacity,
                                     uint8_t* new_seg, uint8_t* tmp_seg,
@@ -734,6 +736,102 @@ __global__ void check_w_kernel(V_ID vp, V_ID row_left,
   if (threadIdx.x == 0 && cnt) atomicAdd(mistakes, cnt);
 }
 
+// ---------------- bucketed schedule (near-far delta-stepping) ----------
+// The one O(vp) pass of a bucketed iteration: it classifies every local
+// vertex against the device-resident `limit` and replaces build_bitmap, the
+// snapshot stream copy and any queue the scatter would have appended.
+//
+//   changed = snapshot[v] != label[v]
+//   d       = changed | (replace ? 0 : dirty bit)   (pull: dirty = changed)
+//   active  = d && label[v] <= *limit               -> seg's dense bitmap
+//   dirty   = d && !active                          (the deferred set)
+//   snapshot[v] = label[v]                          (standing invariant)
+//
+// One lane per vertex; a wave owns vertices [64w, 64w + 64) and forms its
+// two words with __ballot: one u64 of dirty and one u64 of the bitmap (at
+// seg + 8, 8-byte aligned), each stored by lane 0 — so dirty holds
+// 2 * ceil(vp / 64) u32 words and the bitmap ceil(vp / 64) u64 words, and
+// bits at and beyond vp are written 0. Counts and the minimum deferred
+// label accumulate per lane over the grid-stride loop, then one block
+// ladder and one atomic per block: active -> header numNodes, deferred ->
+// meta[7], min deferred label -> meta[6] (the caller presets numNodes = 0,
+// meta[6] = INF_LABEL, meta[7] = 0). With snapshot == labels everywhere the
+// pass is the bucket advance's reselect.
+__global__ void bucket_select_kernel(V_ID vp, uint32_t* snapshot,
+                                     const uint32_t* labels_part,
+                                     uint32_t* dirty, const uint32_t* limit_p,
+                                     int replace, uint8_t* seg,
+                                     uint32_t* meta) {
+  __shared__ uint32_t lds_a[BLOCK / WAVE];
+  __shared__ uint32_t lds_d[BLOCK / WAVE];
+  __shared__ uint32_t lds_m[BLOCK / WAVE];
+  const uint32_t limit = *limit_p;
+  unsigned long long* dirty64 = (unsigned long long*)dirty;
+  unsigned long long* bitmap64 =
+      (unsigned long long*)(seg + sizeof(FrontierHeader));
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  uint32_t n_active = 0, n_defer = 0, min_defer = INF_LABEL;
+  const uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  // block-uniform loop bound: every lane of a wave reaches the ballots
+  for (uint64_t blk = (uint64_t)blockIdx.x * blockDim.x; blk < vp;
+       blk += stride) {
+    uint64_t v = blk + threadIdx.x;
+    uint64_t wbase = blk + (uint64_t)wid * WAVE;  // wave-uniform
+    if (wbase >= vp) continue;  // whole wave past the end: no word to own
+    uint64_t word = wbase >> 6;
+    bool in = v < vp;
+    uint32_t snap = 0, lab = 0;
+    if (in) {
+      snap = snapshot[v];
+      lab = labels_part[v];
+    }
+    bool d = in && snap != lab;
+    if (d) snapshot[v] = lab;
+    if (!replace) {
+      unsigned long long old = dirty64[word];
+      d = d || (in && ((old >> lane) & 1ull));
+    }
+    bool act = d && lab <= limit;
+    bool def = d && !act;
+    unsigned long long act_word = __ballot(act);
+    unsigned long long def_word = __ballot(def);
+    if (lane == 0) {
+      bitmap64[word] = act_word;
+      dirty64[word] = def_word;
+    }
+    n_active += act;
+    if (def) {
+      n_defer++;
+      min_defer = lab < min_defer ? lab : min_defer;
+    }
+  }
+  // block ladder (gpu_common.h shape): wave reduce, one LDS slot per wave,
+  // wave 0 finishes, thread 0 issues the block's atomics
+  n_active = wave_reduce_sum(n_active);
+  n_defer = wave_reduce_sum(n_defer);
+  min_defer = wave_reduce_min(min_defer);
+  if (lane == 0) {
+    lds_a[wid] = n_active;
+    lds_d[wid] = n_defer;
+    lds_m[wid] = min_defer;
+  }
+  __syncthreads();
+  if (wid == 0) {
+    bool has = lane < (int)(blockDim.x / WAVE);
+    n_active = wave_reduce_sum(has ? lds_a[lane] : 0u);
+    n_defer = wave_reduce_sum(has ? lds_d[lane] : 0u);
+    min_defer = wave_reduce_min(has ? lds_m[lane] : INF_LABEL);
+    if (lane == 0) {
+      if (n_active) atomicAdd(&((FrontierHeader*)seg)->numNodes, n_active);
+      if (n_defer) {
+        atomicAdd(&meta[7], n_defer);
+        atomicMin(&meta[6], min_defer);
+      }
+    }
+  }
+}
+
 }  // namespace lux
 
 // ---------------- C ABI ----------------
@@ -954,6 +1052,24 @@ void lux_gpu_check_w(uint64_t stream, V_ID vp, V_ID row_left,
   hipLaunchKernelGGL(check_w_kernel, dim3(grid_for(vp)), dim3(BLOCK), 0, s,
                      vp, row_left, row_ptr_loc, col, weight, labels, source,
                      mistakes);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ---- bucketed schedule ----
+
+// dirty: u32[2 * ceil(vp / 64)] in/out; seg: header + ceil(vp / 64) u64
+// bitmap words, numNodes preset to 0; meta[6] preset to INF_LABEL, meta[7]
+// to 0; limit: one device-resident u32 (captured graphs replay across
+// buckets). lux_gpu_frontier_fixup(built_dense = 1) finishes the segment.
+void lux_gpu_bucket_select(uint64_t stream, V_ID vp, uint32_t* snapshot,
+                           const uint32_t* labels_part, uint32_t* dirty,
+                           const uint32_t* limit, int replace, uint8_t* seg,
+                           uint32_t* meta) {
+  hipStream_t s = (hipStream_t)stream;
+  if (vp == 0) return;
+  hipLaunchKernelGGL(bucket_select_kernel, dim3(grid_for(vp)), dim3(BLOCK), 0,
+                     s, vp, snapshot, labels_part, dirty, limit, replace, seg,
+                     meta);
   LUX_POST_LAUNCH(stream);
 }
 

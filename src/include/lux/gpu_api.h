@@ -230,6 +230,13 @@ void lux_gpu_check_w(uint64_t stream, lux::V_ID vp, lux::V_ID row_left,
                      const lux::E_ID* row_ptr_loc, const lux::V_ID* col,
                      const lux::WeightType* weight, const uint32_t* labels,
                      lux::V_ID source, unsigned long long* mistakes);
+// bucketed (near-far delta-stepping) schedule: the per-iteration O(vp)
+// select pass — active bitmap into seg, deferred set into dirty, counts and
+// the minimum deferred label into seg's header and meta[6..7]
+void lux_gpu_bucket_select(uint64_t stream, lux::V_ID vp, uint32_t* snapshot,
+                           const uint32_t* labels_part, uint32_t* dirty,
+                           const uint32_t* limit, int replace, uint8_t* seg,
+                           uint32_t* meta);
 
 // cf.hip
 void lux_gpu_cf_seed(uint64_t stream, uint64_t n, const float* oldv,
