@@ -16,8 +16,8 @@ int main(int argc, char** argv) {
     // re-exec'd native multi-GPU worker (SGD or MFMA ALS sweeps)
     HostCSC g;
     if (!load_graph(a, &g, true)) return 1;
-    if (a.als && a.k > 64) {
-      fprintf(stderr, "[lux] -als covers K <= 64 (MFMA tile grid)\n");
+    if (a.als && (a.k < 1 || a.k > 128)) {
+      fprintf(stderr, "[lux] -als covers 1 <= K <= 128 (MFMA tile grid)\n");
       return 1;
     }
     return col_filter_multi_child(g, atoi(mr),
@@ -54,8 +54,8 @@ int main(int argc, char** argv) {
 
   hipStream_t s;
   LUX_OK(hipStreamCreate(&s));
-  if (a.als && a.k > 64) {
-    fprintf(stderr, "[lux] -als covers K <= 64 (MFMA tile grid)\n");
+  if (a.als && (a.k < 1 || a.k > 128)) {
+    fprintf(stderr, "[lux] -als covers 1 <= K <= 128 (MFMA tile grid)\n");
     return 1;
   }
   size_t arena_bytes = 8ull * NV + 8ull * NE              // graph + weights
@@ -64,7 +64,7 @@ int main(int argc, char** argv) {
                        + 8ull * NV * a.k                  // old/new vectors
                        + 8ull * (NE / 8192 + NV / 16)
                        + (a.als ? 4ull * NV +             // hub slot map
-                            (17ull << 20) * (NE / 2048 / 1024 + 1) : 0);
+                            als_scratch_bytes(NE, a.k) : 0);
   DeviceArena arena(arena_bytes);
   DeviceGraph dg;
   if (skind) {

@@ -72,7 +72,10 @@ class CFALSEngine:
     """ALS sweeps via MFMA Gram accumulation + per-wave Cholesky
     (src/gpu/cf_als.hip). Same data movement and exchange as CFEngine;
     an alternative optimizer that reaches the SGD fixed point in far fewer
-    sweeps. K <= 64 (the MFMA tile grid is 4x4 of 16x16).
+    sweeps. K <= 128: K <= 64 runs the 4x4 grid of 16x16 MFMA tiles in one
+    wave per row; 64 < K <= 128 runs the 8x8 grid in a 128-thread workgroup
+    per row. The hub scratch pitch KP follows K (64 or 128): gram is
+    nbig x KP x KP (upper triangle), rhs_h is nbig x KP.
 
     When the partition knows the bipartite user/item boundary
     (part.n_users), each sweep is true Gauss-Seidel ALTERNATION: solve all
@@ -86,9 +89,10 @@ class CFALSEngine:
 
     def __init__(self, part: GraphPart, K=64):
         assert part.weight is not None, "CF needs a weighted graph"
-        assert K <= 64, "ALS MFMA path covers K <= 64"
+        assert 1 <= K <= 128, "ALS MFMA path covers K <= 128"
         self.part = part
         self.K = K
+        self.KP = KP = 64 if K <= 64 else 128  # hub scratch pitch
         part.build_bins()
         device = part.device
         self.old = torch.from_numpy(als_init(part.nv, K)).to(device)
@@ -130,9 +134,9 @@ class CFALSEngine:
                                     device=device)
                 slot[self.nbigu:] -= self.nbigu
                 self.hubidx[self.bin2vs.long()] = slot
-            self.gram = torch.empty(part.nbig * 64 * 64, dtype=F32,
+            self.gram = torch.empty(part.nbig * KP * KP, dtype=F32,
                                     device=device)
-            self.rhs_h = torch.empty(part.nbig * 64, dtype=F32,
+            self.rhs_h = torch.empty(part.nbig * KP, dtype=F32,
                                      device=device)
         else:
             self.hubidx = self.gram = self.rhs_h = None
@@ -141,12 +145,14 @@ class CFALSEngine:
         # 2.5x below dword rate, and the dword-pair staging variant loses
         # the register-prefetch pipeline (20.4 vs 10.5 ms/sweep). The
         # fp32-gather + bf16-LDS-stage split is the winning shape.
-        # LUX_ALS_BF_GATHER=1 re-enables the experiment (needs even K).
+        # LUX_ALS_BF_GATHER=1 re-enables the experiment (needs even K;
+        # K <= 64 only — the wide kernels have no replica path).
         import os
         self.old_bf = torch.empty(part.nv * K, dtype=torch.bfloat16,
                                   device=device) \
             if os.environ.get("LUX_ALS_BF_GATHER") == "1" \
-            and K % 2 == 0 and not os.environ.get("LUX_ALS_F32") else None
+            and K % 2 == 0 and K <= 64 \
+            and not os.environ.get("LUX_ALS_F32") else None
 
     def _begin_sweep(self):
         p = self.part
@@ -191,9 +197,9 @@ class CFALSEngine:
                            self.bin2s[self.n2u * 2:], p.nbig - self.nbigu,
                            self.bin2vs[self.nbigu:], self.hubidx,
                            None if self.gram is None
-                           else self.gram[self.nbigu * 64 * 64:],
+                           else self.gram[self.nbigu * self.KP * self.KP:],
                            None if self.rhs_h is None
-                           else self.rhs_h[self.nbigu * 64:],
+                           else self.rhs_h[self.nbigu * self.KP:],
                            p.row_ptr, p.col, p.weight, self.old,
                            self.new_part, p.row_left, self.K,
                            oldv_bf=self.old_bf)

@@ -55,7 +55,7 @@ struct CFAlsArgs {
                          // the hot src-vector table on the bf16 Gram path
   float* newv;           // f32[vp*K] (pre-seeded with old slice)
   V_ID row_left;
-  int K;                 // <= 64
+  int K;                 // <= 64 here, <= 128 in the wide kernels below
 };
 
 struct AlsGramLds {
@@ -588,6 +588,379 @@ __global__ __launch_bounds__(ALS_TB) void cf_als_hub_solve_kernel(
   }
 }
 
+// ======================== 64 < K <= 128 (wide path) ========================
+// Separate kernels, launched only for K > 64; the kernels above are not
+// parameterised over the rank and compile exactly as before.
+//
+// One 128-thread workgroup (two waves) owns one dst vertex: thread = dim =
+// Cholesky row, so one edge's source vector is still one coalesced read
+// (128 x 4 B = 512 B across the workgroup). The Gram is an 8x8 grid of
+// 16x16 tiles, 36 of them on or above the diagonal, split 18/18 between
+// the waves (72 accumulator registers each). Both waves run the SAME
+// unrolled tile list over LOCAL block numbers 0..7; a wave-dependent block
+// permutation (als2_blk) turns them into global 16-dim blocks, so no
+// accumulator is ever indexed by a runtime value:
+//   local tiles   the 10 upper tiles among blocks {0..3}, and
+//                 (x, 4+x), (x, 4+(x+1)%4) for x = 0..3
+//   wave 0        local == global: upper tiles of dims 0..63 plus two
+//                 diagonals of the 4x4 cross panel
+//   wave 1        local b -> b+4 (b < 4), (b-3)&3 (b >= 4): the tiles of
+//                 dims 64..127 plus the cross panel's other two diagonals
+//                 (as their transposes; the Gram is symmetric)
+// Each wave reads all 8 fragments per k-step for its 18 MFMAs.
+//
+// LDS: the factor lives PACKED lower-triangular, L[i][j] at i(i+1)/2 + j,
+// 129 rows (row 128 = rhs, see als2_factor): 33.5 KB instead of the 66 KB
+// of a padded square, and the staging tile ALIASES it (the Gram sits in
+// accumulators until the last tile is consumed) -> 34.5 KB static, so LDS
+// admits 4 workgroups per CU (the Gram kernels' registers, ~250 VGPRs +
+// accumulators at one wave per SIMD, allow 2; a tighter budget spills, and
+// these kernels must not use scratch). Triangular numbers are a bijection mod 2^m,
+// so the 32 lanes of a ds_read_b32 group walking one column (rows i0..i0+31,
+// i0 a multiple of 32) hit 32 distinct banks; row reads are contiguous.
+constexpr int ALS2_K = 128;       // KP: padded rank and hub scratch pitch
+constexpr int ALS2_TB = 128;      // thread = dim = Cholesky row (2 waves)
+constexpr int ALS2_NT = 18;       // tiles per wave
+constexpr int ALS2_SPITCH = 144;  // fp32 stage pitch: 16 mod 32 banks, so a
+                                  // fragment read (2 edge rows x 16 dims per
+                                  // 32-lane group) is conflict-free
+constexpr int ALS2_LSIZE = (ALS2_K + 1) * (ALS2_K + 2) / 2;
+
+__host__ __device__ constexpr int als2_tri(int i) {
+  return i * (i + 1) / 2;
+}
+
+__device__ __forceinline__ int als2_blk(int wv, int b) {
+  return wv ? (b < 4 ? b + 4 : ((b - 3) & 3)) : b;
+}
+
+struct alignas(16) AlsWideStage {
+  union {
+    float S[ALS_TILE * ALS2_SPITCH];   // fp32: row = edge
+    __bf16 Sb[ALS2_K * ALS_BPITCH];    // bf16, TRANSPOSED: row = dim
+  };
+};
+
+struct AlsWideLds {
+  union {
+    AlsWideStage st;
+    float L[ALS2_LSIZE];  // packed lower Gram -> factor; row 128 = rhs -> y
+  };
+  float thr[ALS2_K];      // per-row pivot thresholds
+  float diag[ALS2_K];     // factor diagonal (-1 = deficient pivot)
+};
+
+#define ALS2_TILES_A {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 0, 0, 1, 1, 2, 2, 3, 3}
+#define ALS2_TILES_B {0, 1, 2, 3, 1, 2, 3, 2, 3, 3, 4, 5, 5, 6, 6, 7, 7, 4}
+
+// Gram accumulation over edges [b, e) (workgroup-uniform). Same tile-level
+// software pipeline as als_gram_range: the next tile's gathers issue into
+// registers right before the current tile's MFMA burst. rhs folds from
+// registers in exact fp32 in both modes (tid = dim holds S[r][tid]).
+template <int MODE>
+__device__ __forceinline__ void als2_gram_range(const CFAlsArgs& a, E_ID b,
+                                                E_ID e, int tid,
+                                                AlsWideStage* st,
+                                                f32x4 acc[ALS2_NT],
+                                                float* rhs) {
+  static constexpr int TA[ALS2_NT] = ALS2_TILES_A;
+  static constexpr int TB[ALS2_NT] = ALS2_TILES_B;
+  if (b >= e) return;
+  int lane = tid & (WAVE - 1);
+  int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int rem = (int)(e - b < ALS_TILE ? e - b : (E_ID)ALS_TILE);
+  uint32_t mycol = 0;
+  float myw = 0.0f;
+  if (lane < rem) {  // each wave keeps its own copy for the shuffles
+    mycol = a.col[b + lane];
+    myw = (float)a.w[b + lane];
+  }
+  float tmp[ALS_TILE];
+  als_vec_loads(a, mycol, rem, tid, tmp);
+  int m = lane & 15, g = lane >> 4;
+  int fo[8];  // per-fragment LDS offsets of this wave's blocks
+#pragma unroll
+  for (int t = 0; t < 8; t++)
+    fo[t] = MODE == 1 ? (16 * als2_blk(wv, t) + m) * ALS_BPITCH + g * 8
+                      : g * ALS2_SPITCH + 16 * als2_blk(wv, t) + m;
+  for (E_ID t = b; t < e; t += ALS_TILE) {
+    float r0 = 0.0f, r1 = 0.0f;
+#pragma unroll
+    for (int r = 0; r < ALS_TILE; r += 2) {
+      r0 += __shfl(myw, r, WAVE) * tmp[r];
+      r1 += __shfl(myw, r + 1, WAVE) * tmp[r + 1];
+    }
+    *rhs += r0 + r1;
+    int rem_cur = rem;
+    if (MODE == 1) {
+      uint32_t* row32 = (uint32_t*)&st->Sb[(uint32_t)tid * ALS_BPITCH];
+#pragma unroll
+      for (int w = 0; w < ALS_TILE / 2; w++) {
+        union {
+          __bf16 h[2];
+          uint32_t u;
+        } pk;
+        pk.h[0] = (__bf16)tmp[2 * w];
+        pk.h[1] = (__bf16)tmp[2 * w + 1];
+        row32[w] = pk.u;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < ALS_TILE; r++)
+        st->S[r * ALS2_SPITCH + tid] = tmp[r];
+    }
+    // prefetch next tile's col/weight, then its vectors
+    E_ID t2 = t + ALS_TILE;
+    bool more = t2 < e;
+    uint32_t ncol = 0;
+    float nw = 0.0f;
+    if (more) {
+      rem = (int)(e - t2 < ALS_TILE ? e - t2 : (E_ID)ALS_TILE);
+      if (lane < rem) {
+        ncol = a.col[t2 + lane];
+        nw = (float)a.w[t2 + lane];
+      }
+    }
+    __syncthreads();
+    if (MODE == 1) {
+      bf16x8 f[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) f[i] = *(const bf16x8*)&st->Sb[fo[i]];
+      if (more) {
+        myw = nw;
+        als_vec_loads(a, ncol, rem, tid, tmp);
+        mycol = ncol;
+      }
+#pragma unroll
+      for (int i = 0; i < ALS2_NT; i++)
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[TA[i]], f[TB[i]],
+                                                         acc[i], 0, 0, 0);
+    } else {
+      if (more) {
+        myw = nw;
+        als_vec_loads(a, ncol, rem, tid, tmp);
+        mycol = ncol;
+      }
+      int rem4 = (rem_cur + 3) & ~3;  // rows >= rem_cur are staged zeros
+      for (int kk = 0; kk < rem4; kk += 4) {
+        const float* base = &st->S[kk * ALS2_SPITCH];
+        float f[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) f[i] = base[fo[i]];
+#pragma unroll
+        for (int i = 0; i < ALS2_NT; i++)
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[TA[i]], f[TB[i]],
+                                                        acc[i], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // tile consumed before the next stage overwrites
+  }
+}
+
+// In-place factor + solve of the packed 128-row system; every thread of the
+// workgroup calls it. On entry L holds the lower triangle of G (regulariser
+// and identity padding applied, thr[] set) and row 128 holds the rhs.
+//
+// Left-looking Cholesky: step k finishes COLUMN k,
+//   L[i][k] = (G[i][k] - sum_{j<k} L[i][j] L[k][j]) / L[k][k],
+// a read-only dot product per row (four independent chains) and ONE
+// workgroup barrier per step, where the 64-row right-looking update would
+// need two barriers and an LDS read-modify-write per element. Every thread
+// folds the pivot's own sum of squares from the row-k values it reads
+// anyway, so the pivot test needs no broadcast. Thread 0 has no column work
+// after step 0 and carries the rhs as row 128: the same recurrence leaves
+// y = L^-1 rhs there, which is the forward solve.
+//
+// The pivot rule is wave_cholesky64's: threshold max(lambda/2,
+// ALS_PIVOT_RTOL * G_kk) from the diagonal BEFORE elimination; a deficient
+// pivot gets the -1 sentinel, a zeroed column (y_k included) and no step in
+// the backward solve. The factor diagonal goes to diag[] so step k never
+// writes an element its own readers still need.
+//
+// The backward solve L^T d = y runs in wave 0 alone with two dims per lane
+// (lane, lane + 64): pivots broadcast by shuffle, no barriers.
+__device__ __forceinline__ void als2_factor_solve(AlsWideLds* lds, int tid,
+                                                  const CFAlsArgs& a,
+                                                  V_ID v) {
+  float* L = lds->L;
+  int row = tid == 0 ? ALS2_K : tid;
+  float* Li = &L[als2_tri(row)];
+  for (int k = 0; k < ALS2_K; k++) {
+    if (row >= k) {
+      const float* Lk = &L[als2_tri(k)];
+      // 8 elements per trip, all 16 LDS reads issued before the first FMA:
+      // the loop is latency-bound, not throughput-bound
+      float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+      float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, d3 = 0.0f;
+      for (int j = 0; j < k; j += 8) {
+        float kv[8], lv[8];
+        if (j + 8 <= k) {
+#pragma unroll
+          for (int u = 0; u < 8; u++) kv[u] = Lk[j + u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) lv[u] = Li[j + u];
+        } else {  // ragged tail: elements at or past k count as zero
+#pragma unroll
+          for (int u = 0; u < 8; u++) kv[u] = j + u < k ? Lk[j + u] : 0.0f;
+#pragma unroll
+          for (int u = 0; u < 8; u++) lv[u] = j + u < k ? Li[j + u] : 0.0f;
+        }
+        d0 += kv[0] * kv[0] + kv[4] * kv[4];
+        d1 += kv[1] * kv[1] + kv[5] * kv[5];
+        d2 += kv[2] * kv[2] + kv[6] * kv[6];
+        d3 += kv[3] * kv[3] + kv[7] * kv[7];
+        s0 += lv[0] * kv[0] + lv[4] * kv[4];
+        s1 += lv[1] * kv[1] + lv[5] * kv[5];
+        s2 += lv[2] * kv[2] + lv[6] * kv[6];
+        s3 += lv[3] * kv[3] + lv[7] * kv[7];
+      }
+      float piv = Lk[k] - ((d0 + d1) + (d2 + d3));
+      bool ok = piv > lds->thr[k];
+      float dkk = ok ? sqrtf(piv) : 1.0f;
+      if (row > k)
+        Li[k] = ok ? (Li[k] - ((s0 + s1) + (s2 + s3))) / dkk : 0.0f;
+      if (tid == k) lds->diag[k] = ok ? dkk : -1.0f;
+    }
+    __syncthreads();
+  }
+  if (tid < WAVE) {
+    const float* y = &L[als2_tri(ALS2_K)];
+    float r0 = y[tid], r1 = y[tid + WAVE];
+    for (int k = ALS2_K - 1; k >= WAVE; k--) {
+      float lkk = lds->diag[k];
+      float dk = lkk > 0.0f ? __shfl(r1, k - WAVE, WAVE) / lkk : 0.0f;
+      const float* Lk = &L[als2_tri(k)];
+      if (tid + WAVE == k) r1 = dk;
+      else if (tid + WAVE < k) r1 -= Lk[tid + WAVE] * dk;
+      r0 -= Lk[tid] * dk;
+    }
+    for (int k = WAVE - 1; k >= 0; k--) {
+      float lkk = lds->diag[k];
+      float dk = lkk > 0.0f ? __shfl(r0, k, WAVE) / lkk : 0.0f;
+      if (tid == k) r0 = dk;
+      else if (tid < k) r0 -= L[als2_tri(k) + tid] * dk;
+    }
+    if (tid < a.K) a.newv[(uint64_t)v * a.K + tid] = r0;
+    if (tid + WAVE < a.K) a.newv[(uint64_t)v * a.K + tid + WAVE] = r1;
+  }
+  __syncthreads();  // L is free for the next vertex's stage / load
+}
+
+// Regulariser, identity padding for dims >= K, thresholds and the rhs row.
+// Each thread touches only its own diagonal; the caller has made the
+// triangle visible.
+__device__ __forceinline__ void als2_finish_gram(AlsWideLds* lds, int tid,
+                                                 int K, float rhs) {
+  float d = tid < K ? lds->L[als2_tri(tid) + tid] + (float)CF_LAMBDA : 1.0f;
+  lds->L[als2_tri(tid) + tid] = d;
+  lds->thr[tid] = fmaxf((float)CF_LAMBDA * 0.5f, ALS_PIVOT_RTOL * d);
+  lds->L[als2_tri(ALS2_K) + tid] = rhs;
+  __syncthreads();
+}
+
+// ---- one workgroup per vertex: gram + solve fused (deg < T2 bin lists) ----
+template <int MODE>
+__global__ __launch_bounds__(ALS2_TB) void cf_als_wide_solve_kernel(
+    uint32_t n, const V_ID* binlist, CFAlsArgs a) {
+  static constexpr int TA[ALS2_NT] = ALS2_TILES_A;
+  static constexpr int TB[ALS2_NT] = ALS2_TILES_B;
+  __shared__ AlsWideLds lds;
+  int tid = threadIdx.x;
+  int lane = tid & (WAVE - 1);
+  int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    V_ID v = binlist[i];
+    E_ID b = a.row_ptr[v], e = a.row_ptr[v + 1];
+    f32x4 acc[ALS2_NT];
+#pragma unroll
+    for (int t = 0; t < ALS2_NT; t++) acc[t] = {0, 0, 0, 0};
+    float rhs = 0.0f;
+    als2_gram_range<MODE>(a, b, e, tid, &lds.st, acc, &rhs);
+    // accumulators -> packed lower triangle (C/D map of both MFMA shapes:
+    // row = (lane>>4)*4 + reg, col = lane&15); a diagonal tile keeps its
+    // lower half only
+    int row = (lane >> 4) * 4, col = lane & 15;
+#pragma unroll
+    for (int t = 0; t < ALS2_NT; t++) {
+#pragma unroll
+      for (int reg = 0; reg < 4; reg++) {
+        int gr = als2_blk(wv, TA[t]) * 16 + row + reg;
+        int gc = als2_blk(wv, TB[t]) * 16 + col;
+        int hi = gr > gc ? gr : gc, lo = gr > gc ? gc : gr;
+        if (TA[t] != TB[t] || gr >= gc)
+          lds.L[als2_tri(hi) + lo] = acc[t][reg];
+      }
+    }
+    __syncthreads();
+    als2_finish_gram(&lds, tid, a.K, rhs);
+    als2_factor_solve(&lds, tid, a, v);
+  }
+}
+
+// ---- hub path: one workgroup per 8192-edge chunk, Gram into scratch ----
+// gram_scratch: f32[nbig * 128 * 128], upper triangle only, rows/cols >= K
+// never touched (stay zero); rhs_scratch: f32[nbig * 128].
+template <int MODE>
+__global__ __launch_bounds__(ALS2_TB) void cf_als_wide_gram_chunk_kernel(
+    uint32_t n2, const uint2* bin2, V_ID chunk_edges, const int* hubidx,
+    float* gram_scratch, float* rhs_scratch, CFAlsArgs a) {
+  static constexpr int TA[ALS2_NT] = ALS2_TILES_A;
+  static constexpr int TB[ALS2_NT] = ALS2_TILES_B;
+  __shared__ AlsWideStage st;
+  int tid = threadIdx.x;
+  int lane = tid & (WAVE - 1);
+  int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (uint32_t i = blockIdx.x; i < n2; i += gridDim.x) {
+    uint2 ent = bin2[i];
+    V_ID v = ent.x;
+    E_ID b = a.row_ptr[v] + (E_ID)ent.y * chunk_edges;
+    E_ID e = a.row_ptr[v + 1];
+    if (e > b + chunk_edges) e = b + chunk_edges;
+    f32x4 acc[ALS2_NT];
+#pragma unroll
+    for (int t = 0; t < ALS2_NT; t++) acc[t] = {0, 0, 0, 0};
+    float rhs = 0.0f;
+    als2_gram_range<MODE>(a, b, e, tid, &st, acc, &rhs);
+    int idx = hubidx[v];
+    float* Gg = gram_scratch + (uint64_t)idx * ALS2_K * ALS2_K;
+    if (tid < a.K) atomicAdd(&rhs_scratch[(uint64_t)idx * ALS2_K + tid], rhs);
+    int row = (lane >> 4) * 4, col = lane & 15;
+#pragma unroll
+    for (int t = 0; t < ALS2_NT; t++) {
+#pragma unroll
+      for (int reg = 0; reg < 4; reg++) {
+        int gr = als2_blk(wv, TA[t]) * 16 + row + reg;
+        int gc = als2_blk(wv, TB[t]) * 16 + col;
+        int hi = gr > gc ? gr : gc, lo = gr > gc ? gc : gr;
+        if ((TA[t] != TB[t] || gc >= gr) && hi < a.K)
+          atomicAdd(&Gg[lo * ALS2_K + hi], acc[t][reg]);
+      }
+    }
+  }
+}
+
+// ---- hub path: per-vertex solve from global scratch ----
+__global__ __launch_bounds__(ALS2_TB) void cf_als_wide_hub_solve_kernel(
+    uint32_t nbig, const V_ID* bin2v, const float* gram_scratch,
+    const float* rhs_scratch, CFAlsArgs a) {
+  __shared__ AlsWideLds lds;
+  int tid = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < nbig; i += gridDim.x) {
+    V_ID v = bin2v[i];
+    const float* Gg = gram_scratch + (uint64_t)i * ALS2_K * ALS2_K;
+    // scratch row r, column tid (upper, tid >= r) -> packed L[tid][r]:
+    // coalesced reads, each thread fills its own packed row
+    for (int r = 0; r <= tid; r++)
+      lds.L[als2_tri(tid) + r] = Gg[r * ALS2_K + tid];
+    als2_finish_gram(&lds, tid, a.K,
+                     rhs_scratch[(uint64_t)i * ALS2_K + tid]);
+    als2_factor_solve(&lds, tid, a, v);
+  }
+}
+
+#undef ALS2_TILES_A
+#undef ALS2_TILES_B
+
 }  // namespace lux
 
 using namespace lux;
@@ -597,6 +970,9 @@ extern "C" {
 // One ALS sweep over my partition. Reuses the pull.hip degree-bin lists;
 // hubidx maps a hub vertex (local id) to its scratch slot [0, nbig).
 // gram_scratch/rhs_scratch must be zeroed before each sweep when nbig > 0.
+// K selects the scratch pitch KP: 64 for K <= 64 (gram nbig*64*64, rhs
+// nbig*64), 128 for 64 < K <= 128 (gram nbig*128*128, rhs nbig*128). K < 1
+// or K > 128 aborts before anything is launched.
 void lux_gpu_cf_als_iter(uint64_t stream, uint32_t n0, const V_ID* bin0,
                          uint32_t n1, const V_ID* bin1, uint32_t n2,
                          const uint2* bin2, uint32_t nbig, const V_ID* bin2v,
@@ -607,8 +983,52 @@ void lux_gpu_cf_als_iter(uint64_t stream, uint32_t n0, const V_ID* bin0,
                          const uint16_t* oldv_bf /*nullable*/, float* newv,
                          V_ID row_left, int K) {
   hipStream_t s = (hipStream_t)stream;
+  if (K < 1 || K > ALS2_K) {
+    fprintf(stderr, "lux_gpu_cf_als_iter: K = %d outside [1, %d]\n", K,
+            ALS2_K);
+    abort();
+  }
   CFAlsArgs a{row_ptr, col, w, oldv, (const __bf16*)oldv_bf, newv, row_left,
               K};
+  if (K > ALS_K) {
+    // Wide path (KP = 128 scratch pitch). Same per-class defaults as below;
+    // the bf16 gather replica (mode 2) is not extended past K = 64, so
+    // oldv_bf is ignored here.
+    a.oldv_bf = nullptr;
+    bool f32 = getenv("LUX_ALS_F32") != nullptr;
+    int mode = !f32 && getenv("LUX_ALS_BF16") ? 1 : 0;
+    int chunk_mode = f32 ? 0 : 1;
+    if (nbig) {
+      dim3 grid(n2 > MAX_GRID ? MAX_GRID : n2);
+      if (chunk_mode == 1)
+        hipLaunchKernelGGL(cf_als_wide_gram_chunk_kernel<1>, grid,
+                           dim3(ALS2_TB), 0, s, n2, bin2, (V_ID)8192, hubidx,
+                           gram_scratch, rhs_scratch, a);
+      else
+        hipLaunchKernelGGL(cf_als_wide_gram_chunk_kernel<0>, grid,
+                           dim3(ALS2_TB), 0, s, n2, bin2, (V_ID)8192, hubidx,
+                           gram_scratch, rhs_scratch, a);
+      hipLaunchKernelGGL(cf_als_wide_hub_solve_kernel,
+                         dim3(nbig > MAX_GRID ? MAX_GRID : nbig),
+                         dim3(ALS2_TB), 0, s, nbig, bin2v, gram_scratch,
+                         rhs_scratch, a);
+    }
+    const V_ID* lists[2] = {bin1, bin0};
+    uint32_t counts[2] = {n1, n0};
+    for (int c = 0; c < 2; c++) {
+      uint32_t n = counts[c];
+      if (!n) continue;
+      dim3 grid(n > MAX_GRID ? MAX_GRID : n);
+      if (mode == 1)
+        hipLaunchKernelGGL(cf_als_wide_solve_kernel<1>, grid, dim3(ALS2_TB),
+                           0, s, n, lists[c], a);
+      else
+        hipLaunchKernelGGL(cf_als_wide_solve_kernel<0>, grid, dim3(ALS2_TB),
+                           0, s, n, lists[c], a);
+    }
+    LUX_POST_LAUNCH(stream);
+    return;
+  }
   // Mode defaults are PER KERNEL CLASS. Fused per-row solves: exact fp32
   // Gram (16x16x4). bf16 Gram noise (~0.4% of ||G||) swamps sigma_min for
   // moderate-degree rows during alternation — measured: item factors jump

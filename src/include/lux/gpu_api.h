@@ -270,6 +270,11 @@ void lux_gpu_uf_flatten(uint64_t stream, lux::V_ID nv, lux::V_ID* parent,
                         lux::V_ID* labels);
 
 // cf_als.hip
+// 1 <= K <= 128; anything else aborts on the host before any launch. K
+// selects the hub scratch pitch KP (64 for K <= 64, 128 above):
+// gram_scratch is f32[nbig * KP * KP] (upper triangle, rows/cols >= K stay
+// zero), rhs_scratch f32[nbig * KP], both zeroed by the caller per sweep.
+// oldv_bf (bf16 gather replica) is used for K <= 64 only.
 void lux_gpu_cf_als_iter(uint64_t stream, uint32_t n0, const lux::V_ID* bin0,
                          uint32_t n1, const lux::V_ID* bin1, uint32_t n2,
                          const lux_uint2* bin2, uint32_t nbig,

@@ -438,7 +438,7 @@ int col_filter_multi_child(const HostCSC& g, int rank, int ngpus,
       8ull * g.nv + 8ull * (g.ne / (ngpus ? ngpus : 1) + 1) * 2
       + 8ull * (uint64_t)g.nv * K  // old + new slack
       + 12ull * g.nv + (96ull << 20)
-      + (als ? 4ull * g.nv + (17ull << 20) * (g.ne / 2048 / 1024 + 1) : 0));
+      + (als ? 4ull * g.nv + als_scratch_bytes(g.ne, K) : 0));
   multi_upload(g, true, arena, &c);
   float* old_ = arena.alloc_n<float>((uint64_t)g.nv * K);
   float* new_ = arena.alloc_n<float>((uint64_t)(c.vp ? c.vp : 1) * K);
@@ -452,6 +452,7 @@ int col_filter_multi_child(const HostCSC& g, int rank, int ngpus,
   }
   int* hubidx = nullptr;
   float *gram = nullptr, *rhs = nullptr;
+  uint64_t kp = als_scratch_pitch(K);  // hub scratch pitch
   // Gauss-Seidel alternation (n_users > 0): split my bin lists at the
   // LOCAL user/item boundary; hub scratch slots become phase-relative
   // (see SingleGpuCF). A rank whose partition is all-items still joins
@@ -465,8 +466,8 @@ int col_filter_multi_child(const HostCSC& g, int rank, int ngpus,
   }
   if (als && c.bins.nbig) {
     hubidx = arena.alloc_n<int>(c.vp ? c.vp : 1);
-    gram = arena.alloc_n<float>((uint64_t)c.bins.nbig * 64 * 64);
-    rhs = arena.alloc_n<float>((uint64_t)c.bins.nbig * 64);
+    gram = arena.alloc_n<float>((uint64_t)c.bins.nbig * kp * kp);
+    rhs = arena.alloc_n<float>((uint64_t)c.bins.nbig * kp);
     std::vector<V_ID> hv(c.bins.nbig);
     LUX_OK(hipMemcpyAsync(hv.data(), c.bins.bin2v, 4ull * c.bins.nbig,
                           hipMemcpyDeviceToHost, c.s));
@@ -505,9 +506,9 @@ int col_filter_multi_child(const HostCSC& g, int rank, int ngpus,
                             4ull * c.vp * K, hipMemcpyDeviceToDevice,
                             c.s));
       if (c.bins.nbig) {
-        LUX_OK(hipMemsetAsync(gram, 0, 4ull * c.bins.nbig * 64 * 64,
+        LUX_OK(hipMemsetAsync(gram, 0, 4ull * c.bins.nbig * kp * kp,
                               c.s));
-        LUX_OK(hipMemsetAsync(rhs, 0, 4ull * c.bins.nbig * 64, c.s));
+        LUX_OK(hipMemsetAsync(rhs, 0, 4ull * c.bins.nbig * kp, c.s));
       }
     }
     if (alt) {
@@ -526,8 +527,8 @@ int col_filter_multi_child(const HostCSC& g, int rank, int ngpus,
             c.bins.n1 - split.n1u, c.bins.bin1 + split.n1u,
             c.bins.n2 - split.n2u, c.bins.bin2 + split.n2u,
             c.bins.nbig - split.nbigu, c.bins.bin2v + split.nbigu, hubidx,
-            gram ? gram + (uint64_t)split.nbigu * 64 * 64 : nullptr,
-            rhs ? rhs + (uint64_t)split.nbigu * 64 : nullptr, c.row_ptr,
+            gram ? gram + (uint64_t)split.nbigu * kp * kp : nullptr,
+            rhs ? rhs + (uint64_t)split.nbigu * kp : nullptr, c.row_ptr,
             c.col, c.w, old_, nullptr, new_, c.rl, K);
       publish();
       continue;

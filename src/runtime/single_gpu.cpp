@@ -631,14 +631,16 @@ SingleGpuCF::SingleGpuCF(const DeviceGraph& g, int K, DeviceArena& arena,
     LUX_OK(hipMemcpyAsync(hubidx_, hidx.data(), sizeof(int) * g.nv,
                           hipMemcpyHostToDevice, s));
     LUX_OK(hipStreamSynchronize(s));  // hidx leaves scope
-    gram_ = arena.alloc_n<float>((size_t)bins_.nbig * 64 * 64);
-    rhs_ = arena.alloc_n<float>((size_t)bins_.nbig * 64);
+    size_t kp = als_scratch_pitch(K);
+    gram_ = arena.alloc_n<float>((size_t)bins_.nbig * kp * kp);
+    rhs_ = arena.alloc_n<float>((size_t)bins_.nbig * kp);
   }
   LUX_OK(hipStreamSynchronize(s));
 }
 
 void SingleGpuCF::iterate(int iters) {
   size_t n = (size_t)g_.nv * K_;
+  size_t kp = als_scratch_pitch(K_);
   for (int it = 0; it < iters; it++) {
     if (als_) {
       // seed: solved rows are overwritten, deg-0 rows keep their vector
@@ -646,10 +648,10 @@ void SingleGpuCF::iterate(int iters) {
                             hipMemcpyDeviceToDevice, s_));
       if (bins_.nbig) {
         LUX_OK(hipMemsetAsync(gram_, 0,
-                              sizeof(float) * (size_t)bins_.nbig * 64 * 64,
+                              sizeof(float) * (size_t)bins_.nbig * kp * kp,
                               s_));
         LUX_OK(hipMemsetAsync(rhs_, 0,
-                              sizeof(float) * (size_t)bins_.nbig * 64, s_));
+                              sizeof(float) * (size_t)bins_.nbig * kp, s_));
       }
       if (nu_) {
         // Gauss-Seidel alternation: users from old_, then items from the
@@ -665,8 +667,8 @@ void SingleGpuCF::iterate(int iters) {
             bins_.n1 - split_.n1u, bins_.bin1 + split_.n1u,
             bins_.n2 - split_.n2u, bins_.bin2 + split_.n2u,
             bins_.nbig - split_.nbigu, bins_.bin2v + split_.nbigu, hubidx_,
-            gram_ ? gram_ + (size_t)split_.nbigu * 64 * 64 : nullptr,
-            rhs_ ? rhs_ + (size_t)split_.nbigu * 64 : nullptr, row_ptr_,
+            gram_ ? gram_ + (size_t)split_.nbigu * kp * kp : nullptr,
+            rhs_ ? rhs_ + (size_t)split_.nbigu * kp : nullptr, row_ptr_,
             g_.src, g_.weight, new_, nullptr, new_, 0, K_);
       } else {
         lux_gpu_cf_als_iter((uint64_t)s_, bins_.n0, bins_.bin0, bins_.n1,

@@ -88,6 +88,17 @@ BinSplit split_bins_at(Bins& b, V_ID lb, hipStream_t s);
 // line; the item solve amplifies null-space noise by 1/lambda and the
 // bf16 path diverges), so the exact-solve optimizer breaks the
 // degeneracy at init. SGD keeps the reference's constant init.
+// ALS hub scratch pitch KP selected by the latent rank (cf_als.hip): gram
+// is nbig x KP x KP, rhs nbig x KP.
+inline size_t als_scratch_pitch(int K) { return K <= 64 ? 64 : 128; }
+
+// Arena bytes for the ALS hub scratch of a partition with `ne` edges: at
+// most ne/2048 + 1 hubs, 17 MB per 1024 of them at KP = 64, x4 at KP = 128.
+inline uint64_t als_scratch_bytes(uint64_t ne, int K) {
+  uint64_t kp = als_scratch_pitch(K);
+  return (17ull << 20) * (kp * kp / 4096) * (ne / 2048 / 1024 + 1);
+}
+
 inline float als_init_val(uint64_t i, int K) {
   uint64_t z = (i + 0x9E3779B97F4A7C15ull) * 0xBF58476D1CE4E5B9ull;
   z ^= z >> 30;
@@ -191,7 +202,7 @@ class SingleGpuCCUnionFind {
 
 class SingleGpuCF {
  public:
-  // als: exact MFMA ALS sweeps (cf_als.hip, K <= 64) instead of SGD.
+  // als: exact MFMA ALS sweeps (cf_als.hip, K <= 128) instead of SGD.
   // n_users > 0 (bipartite boundary) turns each ALS sweep into true
   // Gauss-Seidel alternation: user rows solve against old item factors,
   // item rows against the UPDATED users (exact in place — a bipartite
@@ -210,8 +221,8 @@ class SingleGpuCF {
   Bins bins_;
   float *old_, *new_;
   int* hubidx_ = nullptr;       // ALS hub scratch slot map
-  float* gram_ = nullptr;       // ALS: nbig x 64 x 64
-  float* rhs_ = nullptr;        // ALS: nbig x 64
+  float* gram_ = nullptr;       // ALS: nbig x KP x KP (als_scratch_pitch)
+  float* rhs_ = nullptr;        // ALS: nbig x KP
   V_ID nu_ = 0;                 // bipartite boundary (0 = Jacobi)
   BinSplit split_;              // bin counts below nu_ (alternation)
 };
