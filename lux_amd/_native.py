@@ -280,6 +280,18 @@ def sssp_weighted_check(nv, col_end, src, weight, label, source):
                                        ctypes.c_uint32(source))
 
 
+def bc_cpu(nv, ne, col_end, src, source):
+    depth = np.empty(nv, np.uint32)
+    sigma = np.empty(nv, np.float64)
+    delta = np.empty(nv, np.float64)
+    cpu.lux_bc_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                   ptr(col_end, u64p), ptr(src, u32p),
+                   ctypes.c_uint32(source), ptr(depth, u32p),
+                   ptr(sigma, ctypes.POINTER(ctypes.c_double)),
+                   ptr(delta, ctypes.POINTER(ctypes.c_double)))
+    return depth, sigma, delta
+
+
 def cf_init(nv, K):
     vec = np.empty((nv, K), np.float32)
     cpu.lux_cf_init(ctypes.c_uint32(nv), ctypes.c_int(K), ptr(vec, f32p))

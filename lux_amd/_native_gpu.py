@@ -420,3 +420,42 @@ def uf_union_kth(stream, vp, row_ptr, col, row_left, parent, k):
 def cc_giant_bits(stream, nv, labels, giant, bits):
     lib().lux_gpu_cc_giant_bits(_u64(stream), _u32(nv), dp(labels),
                                 _u32(giant), dp(bits))
+
+
+# ---- betweenness centrality (bc.hip) ----
+
+def bc_init(stream, nv, source, depth, rec, sigma, delta):
+    lib().lux_gpu_bc_init(_u64(stream), _u32(nv), _u32(source), dp(depth),
+                          dp(rec), dp(sigma), dp(delta))
+
+
+def bc_order_hist(stream, nv, depth, row_ptr, levels, cnt, hubrows):
+    lib().lux_gpu_bc_order_hist(_u64(stream), _u32(nv), dp(depth),
+                                dp(row_ptr), _u32(levels), dp(cnt),
+                                dp(hubrows))
+
+
+def bc_order_scatter(stream, nv, depth, row_ptr, levels, cursor, list_):
+    lib().lux_gpu_bc_order_scatter(_u64(stream), _u32(nv), dp(depth),
+                                   dp(row_ptr), _u32(levels), dp(cursor),
+                                   dp(list_))
+
+
+def bc_level(stream, forward, list_, o0, o1, o2, o3, row_ptr, adj, rec,
+             sigma, delta, d, last, edges):
+    """One level of the sigma (forward) or delta (backward) pass; o0..o3
+    are the level's word offsets into the work list. `edges` is the address
+    of one u64 counter."""
+    lib().lux_gpu_bc_level(_u64(stream), ctypes.c_int(int(bool(forward))),
+                           dp(list_), _u64(o0), _u64(o1), _u64(o2), _u64(o3),
+                           dp(row_ptr), dp(adj), dp(rec), dp(sigma),
+                           dp(delta), _u32(d), ctypes.c_int(int(bool(last))),
+                           dp(edges))
+
+
+def bc_check(stream, nv, source, in_ptr, in_adj, out_ptr, out_adj, depth,
+             sigma, delta, rtol, out):
+    lib().lux_gpu_bc_check(_u64(stream), _u32(nv), _u32(source), dp(in_ptr),
+                           dp(in_adj), dp(out_ptr), dp(out_adj), dp(depth),
+                           dp(sigma), dp(delta), ctypes.c_double(rtol),
+                           dp(out))

@@ -30,6 +30,7 @@ class AppArgs:
         self.wmax = 16  # sssp -weighted -synthetic: hash weights in [1, wmax]
         self.delta = 0  # sssp -weighted: bucket width of the bucketed
         #                 (near-far delta-stepping) schedule; 0 = off
+        self.nsrc = 1  # bc: number of sources (-start, -start + 1, ...)
 
 
 def parse_input_args(argv):
@@ -65,6 +66,8 @@ def parse_input_args(argv):
             a.wmax = int(argv[i + 1]); i += 2
         elif f == "-delta":
             a.delta = int(argv[i + 1]); i += 2
+        elif f == "-nsrc":
+            a.nsrc = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

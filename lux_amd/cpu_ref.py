@@ -61,6 +61,19 @@ def sssp_weighted_check(g: Graph, label: np.ndarray, source: int) -> int:
         np.ascontiguousarray(label, np.uint32), source))
 
 
+def betweenness(g: Graph, source: int):
+    """Single-source Brandes in fp64: (depth u32, sigma f64, delta f64).
+    sigma[source] = 1; sigma[v] sums sigma[u] over the in-edges u->v with
+    depth[u] == depth[v] - 1; delta[u] sums sigma[u]/sigma[v] *
+    (1 + delta[v]) over the out-edges u->v with depth[v] == depth[u] + 1.
+    Parallel edges are distinct paths, self-loops never count, unreached
+    vertices have depth INF and sigma = delta = 0, delta[source] is 0, and
+    nothing is halved for symmetric inputs (BCEngine's conventions)."""
+    if not 0 <= source < g.nv:
+        raise ValueError(f"source {source} outside [0, {g.nv})")
+    return nat.bc_cpu(g.nv, g.ne, g.col_end, g.src, source)
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

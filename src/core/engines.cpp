@@ -257,6 +257,60 @@ E_ID sssp_weighted_check(V_ID nv, const E_ID* col_end, const V_ID* src,
   return mistakes;
 }
 
+// ---------- Betweenness centrality (single source, Brandes) ----------
+// fp64 oracle of BCEngine (no reference equivalent). BFS over the out-edges
+// in queue order; sigma grows along every edge into the next level (each
+// occurrence of a parallel edge is a path, a self-loop never leads one level
+// down); delta folds back in reverse queue order. Unreached vertices keep
+// depth INF, sigma 0, delta 0; delta[source] is reported as 0.
+void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+            V_ID source, V_ID* depth, double* sigma, double* delta) {
+  std::vector<E_ID> out_ptr((size_t)nv + 1, 0);
+  for (E_ID i = 0; i < ne; i++) out_ptr[src[i] + 1]++;
+  for (V_ID v = 0; v < nv; v++) out_ptr[v + 1] += out_ptr[v];
+  std::vector<V_ID> out_dst(ne);
+  {
+    std::vector<E_ID> cur(out_ptr.begin(), out_ptr.end() - 1);
+    E_ID b = 0;
+    for (V_ID v = 0; v < nv; v++) {
+      for (E_ID i = b; i < col_end[v]; i++) out_dst[cur[src[i]]++] = v;
+      b = col_end[v];
+    }
+  }
+  for (V_ID v = 0; v < nv; v++) {
+    depth[v] = INF_LABEL;
+    sigma[v] = 0.0;
+    delta[v] = 0.0;
+  }
+  std::vector<V_ID> order;
+  order.reserve(nv);
+  depth[source] = 0;
+  sigma[source] = 1.0;
+  order.push_back(source);
+  for (size_t head = 0; head < order.size(); head++) {
+    V_ID u = order[head];
+    for (E_ID i = out_ptr[u]; i < out_ptr[u + 1]; i++) {
+      V_ID v = out_dst[i];
+      if (depth[v] == INF_LABEL) {
+        depth[v] = depth[u] + 1;
+        order.push_back(v);
+      }
+      if (depth[v] == depth[u] + 1) sigma[v] += sigma[u];
+    }
+  }
+  for (size_t k = order.size(); k-- > 0;) {
+    V_ID u = order[k];
+    double acc = 0.0;
+    for (E_ID i = out_ptr[u]; i < out_ptr[u + 1]; i++) {
+      V_ID v = out_dst[i];
+      if (depth[v] == depth[u] + 1)
+        acc += sigma[u] / sigma[v] * (1.0 + delta[v]);
+    }
+    delta[u] = acc;
+  }
+  delta[source] = 0.0;
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {

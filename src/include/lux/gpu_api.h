@@ -285,4 +285,32 @@ void lux_gpu_cf_als_iter(uint64_t stream, uint32_t n0, const lux::V_ID* bin0,
                          const uint16_t* oldv_bf /*nullable*/, float* newv,
                          lux::V_ID row_left, int K);
 
+// bc.hip (betweenness centrality, single rank)
+// Records: lux_uint2[nv] {depth, value}. Level order: a counting sort of the
+// reached rows by key = depth*3 + degree bin into a u32 word list (a row id
+// per thread/wave-bin row, a {row, chunk} pair per hub chunk); cnt and the
+// scanned offsets are in words.
+void lux_gpu_bc_init(uint64_t stream, lux::V_ID nv, lux::V_ID source,
+                     const uint32_t* depth, lux_uint2* rec, float* sigma,
+                     float* delta);
+void lux_gpu_bc_order_hist(uint64_t stream, lux::V_ID nv,
+                           const uint32_t* depth, const lux::E_ID* row_ptr,
+                           uint32_t levels, uint32_t* cnt,
+                           unsigned long long* hubrows);
+void lux_gpu_bc_order_scatter(uint64_t stream, lux::V_ID nv,
+                              const uint32_t* depth, const lux::E_ID* row_ptr,
+                              uint32_t levels, unsigned long long* cursor,
+                              uint32_t* list);
+void lux_gpu_bc_level(uint64_t stream, int forward, const uint32_t* list,
+                      uint64_t o0, uint64_t o1, uint64_t o2, uint64_t o3,
+                      const lux::E_ID* row_ptr, const lux::V_ID* adj,
+                      lux_uint2* rec, float* sigma, float* delta, uint32_t d,
+                      int last, unsigned long long* edges);
+void lux_gpu_bc_check(uint64_t stream, lux::V_ID nv, lux::V_ID source,
+                      const lux::E_ID* in_ptr, const lux::V_ID* in_adj,
+                      const lux::E_ID* out_ptr, const lux::V_ID* out_adj,
+                      const uint32_t* depth, const float* sigma,
+                      const float* delta, double rtol,
+                      unsigned long long* out);
+
 }  // extern "C"
