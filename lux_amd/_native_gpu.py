@@ -328,6 +328,45 @@ def pull_finish_pr_active(stream, na, active, acc, out, deg, row_left,
                                         ctypes.c_float(init_rank))
 
 
+def pull_hot_col(stream, n, col, pos, hcol):
+    lib().lux_gpu_pull_hot_col(_u64(stream), _u64(n), dp(col), dp(pos),
+                               dp(hcol))
+
+
+def pull_stream_copy_hot(stream, n0, rng0, off0, col, pos, scol0):
+    lib().lux_gpu_pull_stream_copy_hot(_u64(stream), _u32(n0), dp(rng0),
+                                       dp(off0), dp(col), dp(pos), dp(scol0))
+
+
+def pull_hot_apos(stream, na, active, pos, deg, row_left, apos):
+    lib().lux_gpu_pull_hot_apos(_u64(stream), _u32(na), dp(active), dp(pos),
+                                dp(deg), _u32(row_left), dp(apos))
+
+
+def pull_hot_scatter(stream, nv, pos, old, gold):
+    lib().lux_gpu_pull_hot_scatter(_u64(stream), _u32(nv), dp(pos), dp(old),
+                                   dp(gold))
+
+
+def pull_finish_pr_active_hot(stream, na, active, apos, acc, out, gold, deg,
+                              row_left, init_rank):
+    lib().lux_gpu_pull_finish_pr_active_hot(
+        _u64(stream), _u32(na), dp(active), dp(apos), dp(acc), dp(out),
+        dp(gold), dp(deg), _u32(row_left), ctypes.c_float(init_rank))
+
+
+def pull_slots_stream_hot_iter(stream, n0, cidx0, nt, tile0, off0, scol0, n1,
+                               cidx1, rng1, n2, cidx2, rng2, col, gold, acc,
+                               lo, hi, k):
+    rc = lib().lux_gpu_pull_slots_stream_hot_iter(
+        _u64(stream), _u32(n0), dp(cidx0), _u32(nt), dp(tile0), dp(off0),
+        dp(scol0), _u32(n1), dp(cidx1), dp(rng1), _u32(n2), dp(cidx2),
+        dp(rng2), dp(col), dp(gold), dp(acc), _u32(lo), _u32(hi),
+        ctypes.c_int(k))
+    if rc != 0:
+        raise ValueError(f"pull_slots_stream_hot_iter: unsupported k={k}")
+
+
 def pull_fill_inactive_pr(stream, vp, row_ptr, out, deg, row_left,
                           init_rank):
     lib().lux_gpu_pull_fill_inactive_pr(_u64(stream), _u32(vp), dp(row_ptr),

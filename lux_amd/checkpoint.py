@@ -124,3 +124,7 @@ def _refresh_slice(engine):
         # slot-path PageRank rewrites only rows with in-edges per step; the
         # restored array may hold other values in the rest (step-0 state)
         engine._inactive_done = False
+    if getattr(engine, "_hot", False):
+        # hot-order PageRank gathers from a permuted copy of `old`: the
+        # next step rebuilds it from the restored array
+        engine._gold_stale = True

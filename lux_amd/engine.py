@@ -28,6 +28,12 @@ LLC_BLOCK_SHIFT = 23  # 2^23 verts * 4 B = 32 MB gather window: measured
 # the per-sweep row overhead wins)
 
 PULL_STREAM_DEFAULT = "1"  # LUX_PULL_STREAM when unset (BENCHLOG r4.1)
+PULL_HOT_DEFAULT = "1"  # LUX_PULL_HOT when unset (BENCHLOG r9.1)
+PULL_HOT_LDS_DEFAULT = "2048"  # LUX_PULL_HOT_LDS when unset (BENCHLOG r9.1)
+HOT_BLOCK_SHIFT = 24  # window width of the hot-ordered PageRank sweeps: the
+# gathered part of a window is its first ~40 %, so 64 MB windows hold what
+# 32 MB ones did and halve the acc passes (RMAT-27: 15.04 vs 15.36 ms/iter;
+# id order at this width: 19.9 — every other path stays at LLC_BLOCK_SHIFT)
 
 
 def _bins_for(row_ptr, vp, ep, device, compact=False):
@@ -107,29 +113,64 @@ def pull_stream_enabled():
     return os.environ.get("LUX_PULL_STREAM", PULL_STREAM_DEFAULT) != "0"
 
 
-def run_pull_slots_sweeps(part, oldv, acc, stream=None):
+def pull_hot_enabled():
+    """LUX_PULL_HOT: the single-rank slot sweeps gather in hot order — the
+    sources of every src window ranked by out-degree (GraphPart.
+    prepare_pull_hot), column copies and gather table permuted to match.
+    Same sums bit for bit; =0 / =1 for A/B runs."""
+    import os
+    return os.environ.get("LUX_PULL_HOT", PULL_HOT_DEFAULT) != "0"
+
+
+def pull_hot_lds():
+    """LUX_PULL_HOT_LDS: how many of a window's hottest sources the
+    hot-order stream sweeps keep in LDS (0: none; 2048 or 4096). In hot
+    order they are the first entries of the window's part of the gather
+    table; a gather that lands there never leaves the CU."""
+    import os
+    k = int(os.environ.get("LUX_PULL_HOT_LDS", PULL_HOT_LDS_DEFAULT))
+    if k not in (0, 2048, 4096):
+        raise ValueError(f"LUX_PULL_HOT_LDS={k}: 0, 2048 or 4096")
+    return k
+
+
+def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
+                          hot_lds=0):
     """PR_SUM fold-sweeps on the slot path (GraphPart.prepare_pull_slots):
     one launch per src window, accumulating into the active-row array
     acc[na] — acc[i] belongs to local row part.active[i]. Same window
     order and per-slot fold order as run_pull_sweeps. stream: thread bin
     by the stream role (GraphPart.prepare_pull_stream; None = what
-    LUX_PULL_STREAM says)."""
+    LUX_PULL_STREAM says). hot: sweep the hot-ordered column copies
+    (GraphPart.prepare_pull_hot, built by the caller); oldv is then the
+    gather table in that order, oldv[part.pos[v]] = value of vertex v.
+    hot_lds (hot + stream only): that many of each window's hottest
+    sources are gathered from LDS (pull_hot_lds)."""
     s = _stream()
     if stream is None:
         stream = pull_stream_enabled()
+    col, scol0 = ("hcol", "hscol0") if hot else ("col", "scol0")
     if stream:
-        part.prepare_pull_stream()  # no-op once built (engines: at init)
+        part.prepare_pull_stream(hot=hot)  # no-op once built
+        if hot and hot_lds:
+            for src in part.slot_srcs:
+                ng.pull_slots_stream_hot_iter(
+                    s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
+                    src["off0"], src["hscol0"], src["n1"], src["cidx1"],
+                    src["rng1"], src["n2"], src["cidx2"], src["rng2"],
+                    src["hcol"], oldv, acc, src["lo"], src["hi"], hot_lds)
+            return
         for src in part.slot_srcs:
             ng.pull_slots_stream_iter(
                 s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
-                src["off0"], src["scol0"], src["n1"], src["cidx1"],
+                src["off0"], src[scol0], src["n1"], src["cidx1"],
                 src["rng1"], src["n2"], src["cidx2"], src["rng2"],
-                src["col"], oldv, acc)
+                src[col], oldv, acc)
         return
     for src in part.slot_srcs:
         ng.pull_slots_iter(s, src["n0"], src["cidx0"], src["rng0"],
                            src["n1"], src["cidx1"], src["rng1"], src["n2"],
-                           src["cidx2"], src["rng2"], src["col"], oldv, acc)
+                           src["cidx2"], src["rng2"], src[col], oldv, acc)
 
 
 def seed_pull(part, mode, oldv, newv):
@@ -497,14 +538,16 @@ class GraphPart:
                                self.row_right_all[q] + 1}
         return sorted(bounds)
 
-    def prepare_pull(self, force_shift=None, weighted=False):
+    def prepare_pull(self, force_shift=None, weighted=False, shift=None):
         """Build degree bins and the src-blocked CSC where it pays: when
         the gather window (nv*4 B) exceeds the 256 MiB Infinity Cache
         (LLC-resident sweeps), or when partitioned (rank-local block for
         comm/compute overlap). weighted: the blocked CSC also carries
         self.weight, one view per window next to its col view (weighted
         SSSP pull); a blocked CSC built earlier without weights is built
-        again with them."""
+        again with them. shift: the caller's window width in place of
+        LLC_BLOCK_SHIFT (LUX_BLOCK_SHIFT still overrides it, and the memory
+        guard below still widens it)."""
         self.build_bins()
         weighted = bool(weighted) and self.weight is not None
         blocks = getattr(self, "blocks", None)
@@ -517,7 +560,9 @@ class GraphPart:
             self.build_blocked(bounds, weighted=True)
             return
         shift = force_shift if force_shift is not None else int(
-            __import__("os").environ.get("LUX_BLOCK_SHIFT", LLC_BLOCK_SHIFT))
+            __import__("os").environ.get(
+                "LUX_BLOCK_SHIFT",
+                LLC_BLOCK_SHIFT if shift is None else shift))
         # (r1 widened windows here because the scan size sb*vp overflowed
         # u32 at scale >= 28 — the scan is 64-bit now, so 32 MB windows
         # hold at every scale; VERDICT r1 missing #6.)
@@ -582,7 +627,7 @@ class GraphPart:
         else:
             srcs = [dict(row_ptr=self.row_ptr, row_u32=0, col=self.col,
                          n0=self.n0, n1=self.n1, n2=self.n2, bin0=self.bin0,
-                         bin1=self.bin1, bin2=self.bin2)]
+                         bin1=self.bin1, bin2=self.bin2, lo=0, hi=self.nv)]
         for src in srcs:
             for k, build in (("0", ng.pull_build_slots),
                              ("1", ng.pull_build_slots),
@@ -599,7 +644,7 @@ class GraphPart:
         self.slot_bytes = torch.cuda.memory_allocated(device) - before
         return True
 
-    def prepare_pull_stream(self):
+    def prepare_pull_stream(self, hot=False):
         """Stream-role tables for the thread bin of every slot source (built
         once, after prepare_pull_slots). off0: u32[n0+1] exclusive scan of
         the bin's per-slot edge counts; scol0: the bin's col entries copied
@@ -607,40 +652,110 @@ class GraphPart:
         rows sit in between); tile0: u32[nt+1] first slot of each tile — a
         run of consecutive slots with at most 64 slots and 512 edges, cut
         greedily inside fixed 64-slot groups. Their bytes are added to
-        slot_bytes (and kept apart in stream_bytes)."""
-        if getattr(self, "stream_bytes", None) is not None:
+        slot_bytes (and kept apart in stream_bytes).
+        hot: build hscol0 — scol0 with the hot-order table applied,
+        pos[scol0] (after prepare_pull_hot) — instead of scol0. off0 and
+        tile0 are the same in both orders and built by whichever call
+        comes first; a later call in the other order adds only its column
+        copy (also counted in hot_bytes when hot)."""
+        want = "hscol0" if hot else "scol0"
+        built = getattr(self, "_stream_cols", ())
+        if want in built:
             return
+        assert not hot or getattr(self, "pos", None) is not None, \
+            "prepare_pull_stream(hot=True) needs prepare_pull_hot(deg)"
         device, s = self.device, _stream()
         before = torch.cuda.memory_allocated(device)
         for src in self.slot_srcs:
             n0 = src["n0"]
             if not n0:
                 src["nt"] = 0
-                src["off0"] = src["scol0"] = src["tile0"] = None
+                src["off0"] = src["tile0"] = src[want] = None
+                src.setdefault("scol0", None)
                 continue
-            cnt = torch.empty(n0, dtype=U32, device=device)
-            ng.pull_slot_counts(s, n0, src["rng0"], cnt)
-            ends = torch.empty(n0, dtype=U64, device=device)
-            partials = torch.empty(ng.scan_partials_size(n0), dtype=U64,
-                                   device=device)
-            ng.scan_end_offsets(s, n0, cnt, ends, partials)
-            off0 = torch.zeros(n0 + 1, dtype=U32, device=device)
-            ng.u64_to_u32(s, n0, ends, off0.narrow(0, 1, n0))
-            scol0 = torch.empty(int(ends[n0 - 1].item()), dtype=U32,
-                                device=device)
-            ng.pull_stream_copy(s, n0, src["rng0"], off0, src["col"], scol0)
-            ngroups = (n0 + 63) // 64
-            ng.pull_stream_tile_counts(s, n0, off0, cnt)  # cnt: reused
-            ng.scan_end_offsets(s, ngroups, cnt, ends, partials)
-            nt = int(ends[ngroups - 1].item())
-            tile0 = torch.empty(nt + 1, dtype=U32, device=device)
-            ng.pull_stream_tile_fill(s, n0, off0, ends, tile0)
-            src["nt"], src["off0"], src["scol0"], src["tile0"] = \
-                nt, off0, scol0, tile0
+            if not built:
+                cnt = torch.empty(n0, dtype=U32, device=device)
+                ng.pull_slot_counts(s, n0, src["rng0"], cnt)
+                ends = torch.empty(n0, dtype=U64, device=device)
+                partials = torch.empty(ng.scan_partials_size(n0), dtype=U64,
+                                       device=device)
+                ng.scan_end_offsets(s, n0, cnt, ends, partials)
+                off0 = torch.zeros(n0 + 1, dtype=U32, device=device)
+                ng.u64_to_u32(s, n0, ends, off0.narrow(0, 1, n0))
+                src["ne0"] = int(ends[n0 - 1].item())
+                ngroups = (n0 + 63) // 64
+                ng.pull_stream_tile_counts(s, n0, off0, cnt)  # cnt: reused
+                ng.scan_end_offsets(s, ngroups, cnt, ends, partials)
+                nt = int(ends[ngroups - 1].item())
+                tile0 = torch.empty(nt + 1, dtype=U32, device=device)
+                ng.pull_stream_tile_fill(s, n0, off0, ends, tile0)
+                src["nt"], src["off0"], src["tile0"] = nt, off0, tile0
+                src.setdefault("scol0", None)
+            scol0 = torch.empty(src["ne0"], dtype=U32, device=device)
+            if hot:
+                ng.pull_stream_copy_hot(s, n0, src["rng0"], src["off0"],
+                                        src["col"], self.pos, scol0)
+            else:
+                ng.pull_stream_copy(s, n0, src["rng0"], src["off0"],
+                                    src["col"], scol0)
+            src[want] = scol0
         torch.cuda.synchronize()
         cnt = ends = partials = None
-        self.stream_bytes = torch.cuda.memory_allocated(device) - before
-        self.slot_bytes += self.stream_bytes
+        added = torch.cuda.memory_allocated(device) - before
+        self._stream_cols = tuple(built) + (want,)
+        self.stream_bytes = (getattr(self, "stream_bytes", None) or 0) + added
+        self.slot_bytes += added
+        if hot:  # the column copies alone: off0 / tile0 serve both orders
+            self.hot_bytes += sum(4 * src["hscol0"].numel()
+                                  for src in self.slot_srcs
+                                  if src["hscol0"] is not None)
+
+    def hot_bounds(self):
+        """The src windows the hot order is taken inside: the blocked
+        CSC's bounds list, or the whole vertex range when unblocked."""
+        if self.blocks:
+            return list(self._blk_bounds)
+        return [0, self.nv]
+
+    def prepare_pull_hot(self, deg):
+        """Hot-order tables for the slot sweeps (built once, after
+        prepare_pull_slots). deg: u32[nv] global out-degrees.
+        pos: u32[nv], a permutation that maps every src window of
+        hot_bounds() onto itself, sources by out-degree descending, ties by
+        ascending id — the sources nobody gathers (out-degree 0) end up at
+        the window's tail, the hot ones share full 128-byte lines.
+        hcol (per slot source): pos[col]. apos: u32[na], pos of every active
+        row, 0xFFFFFFFF where its out-degree is 0 (the epilogue's stream).
+        col, scol0 and every other slot / stream table keep their contents.
+        hot_bytes: what the hot order keeps resident — these tables, the
+        hot scol0 (prepare_pull_stream(hot=True)) and the f32[nv] gather
+        table an engine allocates next to them."""
+        if getattr(self, "pos", None) is not None:
+            return
+        device, s, nv = self.device, _stream(), self.nv
+        before = torch.cuda.memory_allocated(device)
+        bounds = self.hot_bounds()
+        ids = torch.arange(nv, dtype=U64, device=device)
+        # one stable sort on (window, ~deg): ids break the ties
+        key = 0xFFFFFFFF - (deg.to(U64) & 0xFFFFFFFF)
+        if len(bounds) > 2:
+            inner = torch.tensor(bounds[1:-1], dtype=U64, device=device)
+            key += torch.bucketize(ids, inner, right=True) << 32
+        order = torch.sort(key, stable=True).indices
+        pos = torch.empty(nv, dtype=U32, device=device)
+        pos[order] = ids.to(U32)
+        del ids, key, order
+        self.pos = pos
+        for src in self.slot_srcs:
+            hcol = torch.empty_like(src["col"])
+            ng.pull_hot_col(s, hcol.numel(), src["col"], pos, hcol)
+            src["hcol"] = hcol
+        self.apos = torch.empty(max(self.na, 1), dtype=U32, device=device)
+        ng.pull_hot_apos(s, self.na, self.active, pos, deg, self.row_left,
+                         self.apos)
+        torch.cuda.synchronize()
+        self.hot_bytes = torch.cuda.memory_allocated(device) - before \
+            + 4 * nv
 
     def build_blocked(self, bounds, weighted=False):
         """Src-blocked CSC build, processed in window GROUPS sized so the
@@ -732,7 +847,8 @@ class GraphPart:
                                         n0=n0, n1=n1, n2=n2, nbig=nbig,
                                         bin0=b0, bin1=b1, bin2=b2,
                                         bin2v=b2v, local=local,
-                                        owner=owner))
+                                        owner=owner, lo=bounds[gb],
+                                        hi=bounds[gb + 1]))
                 if weighted:
                     self.blocks[-1]["weight"] = blk_w.narrow(0, begin,
                                                              end - begin)
@@ -808,8 +924,12 @@ class PagerankEngine:
         # (a degree-descending source permutation was measured here and
         # REGRESSED: 25.5 vs 19.2 ms/iter on RMAT-27 — sorting destroys the
         # generator's natural hot-prefix locality and concentrates the
-        # per-sweep row folds into one window; see BENCHLOG r1)
-        part.prepare_pull()
+        # per-sweep row folds into one window; see BENCHLOG r1. The hot
+        # order below sorts inside every window instead: BENCHLOG r9.1)
+        import os
+        want_hot = (dx.world_size() == 1 and pull_hot_enabled()
+                    and os.environ.get("LUX_PULL_SLOTS", "1") != "0")
+        part.prepare_pull(shift=HOT_BLOCK_SHIFT if want_hot else None)
         # init: rank/deg (deg==0 -> rank), pagerank_gpu.cu:255-259
         rank0 = 1.0 / part.nv
         degf = deg.to(F32)
@@ -820,15 +940,30 @@ class PagerankEngine:
         # fold into acc[na], the epilogue writes `old` in place: no
         # new_part, no slice copy). LUX_PULL_SLOTS=0 keeps the row-table
         # kernels for A/B runs; multi-rank stays on them too.
-        import os
         self._slots = (dx.world_size() == 1
                        and os.environ.get("LUX_PULL_SLOTS", "1") != "0"
                        and part.prepare_pull_slots())
         # LUX_PULL_STREAM=0 keeps the thread-per-slot role for the thread
         # bin of the slot sweeps (A/B runs); default: the stream role
         self._stream_role = bool(self._slots) and pull_stream_enabled()
+        # LUX_PULL_HOT=0 keeps the id-ordered col / scol0 and gathers from
+        # `old` itself (A/B runs); default: sources in hot order inside
+        # every src window, gathered from the permuted copy `gold`
+        self._hot = bool(self._slots) and pull_hot_enabled()
+        if self._hot:
+            part.prepare_pull_hot(deg)
+            self.gold = torch.empty(part.nv, dtype=F32, device=device)
+            # gold follows `old` inside step() (the epilogue writes both);
+            # whatever else writes `old` — the initial state, the inactive
+            # rows' constants, a checkpoint resume — sets this, and the
+            # next step() rebuilds gold from `old` before its sweeps
+            self._gold_stale = True
         if self._stream_role:
-            part.prepare_pull_stream()
+            part.prepare_pull_stream(hot=self._hot)
+        # LUX_PULL_HOT_LDS: the window's hottest sources from LDS (stream
+        # role on hot-ordered tables only)
+        self._hot_lds = pull_hot_lds() \
+            if self._hot and self._stream_role else 0
         if self._slots:
             self.acc = torch.empty(max(part.na, 1), dtype=F32,
                                    device=device)
@@ -860,10 +995,17 @@ class PagerankEngine:
         p = self.part
         if self._slots:
             self.acc.zero_()
-            run_pull_slots_sweeps(p, self.old, self.acc,
-                                  stream=self._stream_role)
+            run_pull_slots_sweeps(p, self.gold if self._hot else self.old,
+                                  self.acc, stream=self._stream_role,
+                                  hot=self._hot, hot_lds=self._hot_lds)
             # the kernel boundary after the last sweep makes the in-place
-            # write safe: nothing reads `old` until the next step's sweeps
+            # write safe: nothing reads `old` (or gold) until the next
+            # step's sweeps
+            if self._hot:
+                ng.pull_finish_pr_active_hot(
+                    _stream(), p.na, p.active, p.apos, self.acc, self.old,
+                    self.gold, self.deg, p.row_left, self.init_rank)
+                return
             ng.pull_finish_pr_active(_stream(), p.na, p.active, self.acc,
                                      self.old, self.deg, p.row_left,
                                      self.init_rank)
@@ -901,6 +1043,11 @@ class PagerankEngine:
                 _publish_async(self, self.new_part).wait()
                 return
             self._steps += 1
+            if self._hot and self._gold_stale:
+                # outside the captured graph, like the fill below
+                ng.pull_hot_scatter(_stream(), p.nv, p.pos, self.old,
+                                    self.gold)
+                self._gold_stale = False
             self._step_single()
             if self._slots and not self._inactive_done:
                 # after the sweeps (they still read the rows' previous
@@ -909,6 +1056,8 @@ class PagerankEngine:
                                          self.old, self.deg, p.row_left,
                                          self.init_rank)
                 self._inactive_done = True
+                # sources with out-edges and no in-edge are gathered
+                self._gold_stale = self._hot
             return
         # overlap: sweep the rank-local src block against cur_part (offset
         # base so global src ids index it) while the gather of remote

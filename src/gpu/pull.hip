@@ -20,6 +20,9 @@
 // accumulating into an array over the rows with in-edges only. Its thread
 // bin can run as the stream role instead (lux_gpu_pull_slots_stream_iter):
 // one wave per tile of consecutive slots, lane = edge, row sums out of LDS.
+// In hot order (sources ranked by out-degree inside each src window) the
+// same sweeps run on permuted column copies and a permuted rank table, and
+// lux_gpu_pull_slots_stream_hot_iter keeps a window's hottest sources in LDS.
 #include "gpu_common.h"
 
 namespace lux {
@@ -179,6 +182,30 @@ struct PullArgsW : PullArgs {
   const WeightType* wgt;
 };
 
+// Hot-order sweeps with the window's K hottest sources in LDS: in hot order
+// they are the K table entries from position lo on, copied by every
+// workgroup once per launch; a gather whose index falls there never leaves
+// the CU (PR_SUM slot sweeps only, see "hot order" below).
+template <int K>
+struct PullArgsHot : PullArgs {
+  V_ID lo;  // first position of the src window
+};
+template <int K>
+__device__ __forceinline__ float* hot_prefix() {
+  __shared__ float hot[K];
+  return hot;
+}
+template <int K>
+__device__ __forceinline__ float hot_load(const float* oldv,
+                                          const float* hot, V_ID lo,
+                                          V_ID c) {
+  // one flat load from a per-lane LDS-or-global address: no branch, so the
+  // four gathers of a batch stay independent loads in flight together
+  V_ID r = c - lo;
+  const float* p = r < (V_ID)K ? hot + r : oldv + c;
+  return *p;
+}
+
 // Result store for the non-atomic bins. The iteration contract: newv is
 // pre-seeded (PR: zeros; labels: the old label slice) before the sweep(s),
 // every sweep — blocked or not — folds its partial in, and PR's epilogue
@@ -251,6 +278,39 @@ __device__ __forceinline__ typename Val<M>::T gather_edges(
     const PullArgsW& a, const typename Val<M>::T* oldv, E_ID j, E_ID e,
     E_ID step) {
   return gather_range_w<M>(oldv, a.col, a.wgt, j, e, step);
+}
+// gather_range<PR_SUM> with the hot prefix served from LDS: same four-way
+// pipeline, same association order, same values
+template <PullMode M, int K>
+__device__ __forceinline__ float gather_edges(const PullArgsHot<K>& a,
+                                              const float* oldv, E_ID j,
+                                              E_ID e, E_ID step) {
+  static_assert(M == PR_SUM, "hot prefix: float sums only");
+  const float* hot = hot_prefix<K>();
+  const V_ID* col = a.col;
+  V_ID lo = a.lo;
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+  for (; j + 3 * step < e; j += 4 * step) {
+    V_ID c0 = col[j], c1 = col[j + step], c2 = col[j + 2 * step],
+         c3 = col[j + 3 * step];
+    a0 = a0 + hot_load<K>(oldv, hot, lo, c0);
+    a1 = a1 + hot_load<K>(oldv, hot, lo, c1);
+    a2 = a2 + hot_load<K>(oldv, hot, lo, c2);
+    a3 = a3 + hot_load<K>(oldv, hot, lo, c3);
+  }
+  for (; j < e; j += step) a0 = a0 + hot_load<K>(oldv, hot, lo, col[j]);
+  return (a0 + a1) + (a2 + a3);
+}
+
+// one gathered value, for the roles that do not go through gather_edges
+__device__ __forceinline__ float old_load(const PullArgs&, const float* oldv,
+                                          V_ID c) {
+  return oldv[c];
+}
+template <int K>
+__device__ __forceinline__ float old_load(const PullArgsHot<K>& a,
+                                          const float* oldv, V_ID c) {
+  return hot_load<K>(oldv, hot_prefix<K>(), a.lo, c);
 }
 
 // ---- where a bin entry's output row and edge range come from ----
@@ -495,11 +555,11 @@ __device__ __forceinline__ float lds_range_sum(const float* v, uint32_t j,
 
 // Wave-local throughout (no __syncthreads()): a wave's LDS accesses issue
 // in order, the wavefront fence only keeps the compiler from moving them.
-template <PullMode M>
+template <PullMode M, typename Args>
 __device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
                                                  const SlotStream& st,
                                                  const V_ID* cidx0,
-                                                 const PullArgs& a) {
+                                                 const Args& a) {
   static_assert(M == PR_SUM, "stream role: float sums only");
   constexpr uint32_t NW = BLOCK / WAVE;
   __shared__ float vals[NW][TILE_EDGES];
@@ -542,10 +602,10 @@ __device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
       V_ID c1 = p1 ? st.scol0[i1] : 0;
       V_ID c2 = p2 ? st.scol0[i2] : 0;
       V_ID c3 = p3 ? st.scol0[i3] : 0;
-      float x0 = oldv[c0];
-      float x1 = p1 ? oldv[c1] : 0.0f;
-      float x2 = p2 ? oldv[c2] : 0.0f;
-      float x3 = p3 ? oldv[c3] : 0.0f;
+      float x0 = old_load(a, oldv, c0);
+      float x1 = p1 ? old_load(a, oldv, c1) : 0.0f;
+      float x2 = p2 ? old_load(a, oldv, c2) : 0.0f;
+      float x3 = p3 ? old_load(a, oldv, c3) : 0.0f;
       v[i0 - e0] = x0;
       if (p1) v[i1 - e0] = x1;
       if (p2) v[i2 - e0] = x2;
@@ -571,6 +631,30 @@ __device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
 template <PullMode M>
 __global__ void __launch_bounds__(BLOCK)
     pull_slots_stream_kernel(SlotBins s, SlotStream st, PullArgs a) {
+  uint32_t blk = blockIdx.x;
+  if (blk < s.g2) {
+    pull_chunk_role<M>(blk, s.g2, s.n2, SlotRows{s.cidx2, s.rng2}, a);
+  } else if (blk < s.g2 + s.g1) {
+    pull_wave_role<M>(blk - s.g2, s.g1, s.n1, SlotRows{s.cidx1, s.rng1}, a);
+  } else {
+    pull_stream_role<M>(blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, st,
+                        s.cidx0, a);
+  }
+}
+
+// pull_slots_stream_kernel on hot-ordered tables with the window's K hottest
+// sources in LDS (a.oldv is gold; [a.lo, hi) the window's positions)
+template <PullMode M, int K>
+__global__ void __launch_bounds__(BLOCK)
+    pull_slots_stream_hot_kernel(SlotBins s, SlotStream st, PullArgsHot<K> a,
+                                 V_ID hi) {
+  float* hot = hot_prefix<K>();
+  const float* oldv = (const float*)a.oldv;
+  for (uint32_t i = threadIdx.x; i < (uint32_t)K; i += BLOCK) {
+    uint64_t p = (uint64_t)a.lo + i;
+    hot[i] = p < hi ? oldv[p] : 0.0f;
+  }
+  __syncthreads();
   uint32_t blk = blockIdx.x;
   if (blk < s.g2) {
     pull_chunk_role<M>(blk, s.g2, s.n2, SlotRows{s.cidx2, s.rng2}, a);
@@ -659,6 +743,62 @@ __global__ void pull_stream_copy_kernel(uint32_t n0, const uint2* rng0,
     uint32_t o = off0[i];
     for (uint32_t j = r.x; j < r.y; j++) scol0[o + (j - r.x)] = col[j];
   }
+}
+
+// ---- hot order: sources ranked by out-degree inside their src window ----
+// pos[v] is a permutation of the vertex ids that maps every src window onto
+// itself (out-degree descending, ties by id). The sweeps then run unchanged
+// on column copies that hold pos[col[j]] and gather from gold, the rank
+// array in that order (gold[pos[v]] = old[v]): a 128-byte line of gold holds
+// 32 sources of like heat instead of one hot source and 31 cold ones, so the
+// same L2 covers more of a window's gathers. Row sums read the same values
+// in the same order as on the id-ordered tables.
+constexpr V_ID HOT_NONE = 0xFFFFFFFFu;  // apos: row is never gathered
+
+// hcol[j] = pos[col[j]]
+__global__ void pull_hot_col_kernel(uint64_t n, const V_ID* col,
+                                    const V_ID* pos, V_ID* hcol) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n;
+       j += stride)
+    hcol[j] = pos[col[j]];
+}
+
+// pull_stream_copy_kernel with pos applied on the way: the stream role's
+// hot-ordered column copy straight from the id-ordered col
+__global__ void pull_stream_copy_hot_kernel(uint32_t n0, const uint2* rng0,
+                                            const uint32_t* off0,
+                                            const V_ID* col, const V_ID* pos,
+                                            V_ID* scol0) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n0;
+       i += stride) {
+    uint2 r = rng0[i];
+    uint32_t o = off0[i];
+    for (uint32_t j = r.x; j < r.y; j++) scol0[o + (j - r.x)] = pos[col[j]];
+  }
+}
+
+// apos[i] = pos of active row i, or HOT_NONE when it has no out-edge (no
+// col entry names it, so its gold cell is never read)
+__global__ void pull_hot_apos_kernel(V_ID na, const V_ID* active,
+                                     const V_ID* pos, const V_ID* deg,
+                                     V_ID row_left, V_ID* apos) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < na;
+       i += stride) {
+    uint64_t g = (uint64_t)row_left + active[i];
+    apos[i] = deg[g] != 0 ? pos[g] : HOT_NONE;
+  }
+}
+
+// gold[pos[v]] = old[v] over all nv vertices
+__global__ void pull_hot_scatter_kernel(V_ID nv, const V_ID* pos,
+                                        const float* old, float* gold) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nv;
+       v += stride)
+    gold[pos[v]] = old[v];
 }
 
 // Greedy cut of the 64-slot group g into tiles of at most TILE_EDGES edges;
@@ -772,6 +912,25 @@ __global__ void pull_finish_pr_active_kernel(V_ID na, const V_ID* active,
        i += stride) {
     uint64_t g = (uint64_t)row_left + active[i];
     out[g] = finish_pr(acc[i], deg[g], init_rank);
+  }
+}
+
+// pull_finish_pr_active_kernel that also keeps the hot-ordered gather table
+// current: the row's new value goes to out[] as before and to gold[apos[i]]
+// (apos: coalesced stream next to active; rows nobody gathers skip the
+// scattered store).
+__global__ void pull_finish_pr_active_hot_kernel(
+    V_ID na, const V_ID* active, const V_ID* apos, const float* acc,
+    float* out, float* gold, const V_ID* deg, V_ID row_left,
+    float init_rank) {
+  uint64_t stride = (uint64_t)blockDim.x * gridDim.x;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < na;
+       i += stride) {
+    uint64_t g = (uint64_t)row_left + active[i];
+    V_ID p = apos[i];
+    float r = finish_pr(acc[i], deg[g], init_rank);
+    out[g] = r;
+    if (p != HOT_NONE) gold[p] = r;
   }
 }
 
@@ -994,6 +1153,40 @@ void lux_gpu_pull_slots_stream_iter(
   LUX_POST_LAUNCH(stream);
 }
 
+// lux_gpu_pull_slots_stream_iter on hot-ordered tables (scol0 / col hold
+// positions, gold is the gather table in that order) with the k hottest
+// sources of the window [lo, hi) kept in LDS; k: 2048 (16 KB with the stream
+// role's tile buffer: still 8 workgroups per CU) or 4096 (6 per CU).
+// Returns 0, or -1 for any other k (nothing is launched).
+int lux_gpu_pull_slots_stream_hot_iter(
+    uint64_t stream, uint32_t n0, const V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const V_ID* scol0,
+    uint32_t n1, const V_ID* cidx1, const uint2* rng1, uint32_t n2,
+    const V_ID* cidx2, const uint2* rng2, const V_ID* col, const float* gold,
+    float* acc, V_ID lo, V_ID hi, int k) {
+  if (k != 2048 && k != 4096) return -1;
+  uint32_t g2 = n2 ? (n2 > (uint32_t)MAX_GRID ? MAX_GRID : n2) : 0;
+  uint32_t g1 = n1 ? grid_for((uint64_t)n1 * WAVE) : 0;
+  uint32_t g0 = n0 && nt ? grid_for((uint64_t)nt * WAVE) : 0;
+  if (g0 + g1 + g2 == 0) return 0;
+  SlotBins sb{n0, n1, n2, g1, g2, cidx0, cidx1, cidx2, nullptr, rng1, rng2};
+  SlotStream st{g0 ? nt : 0, tile0, off0, scol0};
+#define LUX_HOT(K_)                                                           \
+  do {                                                                        \
+    PullArgsHot<K_> a{{nullptr, col, gold, acc, nullptr, 0, 0.0f}, lo};       \
+    hipLaunchKernelGGL((pull_slots_stream_hot_kernel<PR_SUM, K_>),            \
+                       dim3(g0 + g1 + g2), dim3(BLOCK), 0,                    \
+                       (hipStream_t)stream, sb, st, a, hi);                   \
+  } while (0)
+  switch (k) {
+    case 2048: LUX_HOT(2048); break;
+    default: LUX_HOT(4096); break;
+  }
+#undef LUX_HOT
+  LUX_POST_LAUNCH(stream);
+  return 0;
+}
+
 void lux_gpu_pull_finish_pr_active(uint64_t stream, V_ID na,
                                    const V_ID* active, const float* acc,
                                    float* out, const V_ID* deg, V_ID row_left,
@@ -1002,6 +1195,62 @@ void lux_gpu_pull_finish_pr_active(uint64_t stream, V_ID na,
   hipLaunchKernelGGL(pull_finish_pr_active_kernel, dim3(grid_for(na)),
                      dim3(BLOCK), 0, (hipStream_t)stream, na, active, acc,
                      out, deg, row_left, init_rank);
+  LUX_POST_LAUNCH(stream);
+}
+
+// ---- hot order (sources by out-degree inside each src window) ----
+
+// hcol[j] = pos[col[j]], j < n: one window's column copy in hot order
+void lux_gpu_pull_hot_col(uint64_t stream, uint64_t n, const V_ID* col,
+                          const V_ID* pos, V_ID* hcol) {
+  if (!n) return;
+  hipLaunchKernelGGL(pull_hot_col_kernel, dim3(grid_for(n)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, n, col, pos, hcol);
+  LUX_POST_LAUNCH(stream);
+}
+
+// lux_gpu_pull_stream_copy with scol0 = pos[...] of the same col entries
+void lux_gpu_pull_stream_copy_hot(uint64_t stream, uint32_t n0,
+                                  const uint2* rng0, const uint32_t* off0,
+                                  const V_ID* col, const V_ID* pos,
+                                  V_ID* scol0) {
+  if (!n0) return;
+  hipLaunchKernelGGL(pull_stream_copy_hot_kernel, dim3(grid_for(n0)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, n0, rng0, off0, col,
+                     pos, scol0);
+  LUX_POST_LAUNCH(stream);
+}
+
+// apos: u32[na], pos of every active row (0xFFFFFFFF: out-degree 0)
+void lux_gpu_pull_hot_apos(uint64_t stream, V_ID na, const V_ID* active,
+                           const V_ID* pos, const V_ID* deg, V_ID row_left,
+                           V_ID* apos) {
+  if (!na) return;
+  hipLaunchKernelGGL(pull_hot_apos_kernel, dim3(grid_for(na)), dim3(BLOCK), 0,
+                     (hipStream_t)stream, na, active, pos, deg, row_left,
+                     apos);
+  LUX_POST_LAUNCH(stream);
+}
+
+// gold[pos[v]] = old[v], v < nv (pos: a permutation of 0..nv-1)
+void lux_gpu_pull_hot_scatter(uint64_t stream, V_ID nv, const V_ID* pos,
+                              const float* old, float* gold) {
+  if (!nv) return;
+  hipLaunchKernelGGL(pull_hot_scatter_kernel, dim3(grid_for(nv)), dim3(BLOCK),
+                     0, (hipStream_t)stream, nv, pos, old, gold);
+  LUX_POST_LAUNCH(stream);
+}
+
+// lux_gpu_pull_finish_pr_active that also stores each row to gold[apos[i]]
+void lux_gpu_pull_finish_pr_active_hot(uint64_t stream, V_ID na,
+                                       const V_ID* active, const V_ID* apos,
+                                       const float* acc, float* out,
+                                       float* gold, const V_ID* deg,
+                                       V_ID row_left, float init_rank) {
+  if (!na) return;
+  hipLaunchKernelGGL(pull_finish_pr_active_hot_kernel, dim3(grid_for(na)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, na, active, apos,
+                     acc, out, gold, deg, row_left, init_rank);
   LUX_POST_LAUNCH(stream);
 }
 

@@ -150,6 +150,36 @@ void lux_gpu_pull_finish_pr_active(uint64_t stream, lux::V_ID na,
                                    const lux::V_ID* active, const float* acc,
                                    float* out, const lux::V_ID* deg,
                                    lux::V_ID row_left, float init_rank);
+// hot order: sources ranked by out-degree inside their src window (pos, a
+// window-preserving permutation); column copies hold pos[col], the sweeps
+// gather from gold[pos[v]] = old[v], the epilogue keeps gold current
+void lux_gpu_pull_hot_col(uint64_t stream, uint64_t n, const lux::V_ID* col,
+                          const lux::V_ID* pos, lux::V_ID* hcol);
+void lux_gpu_pull_stream_copy_hot(uint64_t stream, uint32_t n0,
+                                  const lux_uint2* rng0,
+                                  const uint32_t* off0, const lux::V_ID* col,
+                                  const lux::V_ID* pos, lux::V_ID* scol0);
+void lux_gpu_pull_hot_apos(uint64_t stream, lux::V_ID na,
+                           const lux::V_ID* active, const lux::V_ID* pos,
+                           const lux::V_ID* deg, lux::V_ID row_left,
+                           lux::V_ID* apos);
+void lux_gpu_pull_hot_scatter(uint64_t stream, lux::V_ID nv,
+                              const lux::V_ID* pos, const float* old,
+                              float* gold);
+void lux_gpu_pull_finish_pr_active_hot(uint64_t stream, lux::V_ID na,
+                                       const lux::V_ID* active,
+                                       const lux::V_ID* apos,
+                                       const float* acc, float* out,
+                                       float* gold, const lux::V_ID* deg,
+                                       lux::V_ID row_left, float init_rank);
+// hot-order stream sweep with the k hottest sources of the window [lo, hi)
+// in LDS (k: 2048 / 4096, else -1 and no launch)
+int lux_gpu_pull_slots_stream_hot_iter(
+    uint64_t stream, uint32_t n0, const lux::V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const lux::V_ID* scol0,
+    uint32_t n1, const lux::V_ID* cidx1, const lux_uint2* rng1, uint32_t n2,
+    const lux::V_ID* cidx2, const lux_uint2* rng2, const lux::V_ID* col,
+    const float* gold, float* acc, lux::V_ID lo, lux::V_ID hi, int k);
 void lux_gpu_pull_fill_inactive_pr(uint64_t stream, lux::V_ID vp,
                                    const lux::E_ID* row_ptr, float* out,
                                    const lux::V_ID* deg, lux::V_ID row_left,
