@@ -319,3 +319,12 @@ def cf_loss(nv, ne, col_end, src, w, K, vec):
     return cpu.lux_cf_loss(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
                            ptr(col_end, u64p), ptr(src, u32p), ptr(w, i32p),
                            ctypes.c_int(K), ptr(vec, f32p))
+
+
+def tc_cpu(nv, ne, col_end, src):
+    total = np.zeros(1, np.uint64)
+    per_vertex = np.empty(nv, np.uint64)
+    cpu.lux_tc_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                   ptr(col_end, u64p), ptr(src, u32p), ptr(total, u64p),
+                   ptr(per_vertex, u64p))
+    return int(total[0]), per_vertex

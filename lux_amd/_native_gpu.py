@@ -498,3 +498,37 @@ def bc_check(stream, nv, source, in_ptr, in_adj, out_ptr, out_adj, depth,
                            dp(in_adj), dp(out_ptr), dp(out_adj), dp(depth),
                            dp(sigma), dp(delta), ctypes.c_double(rtol),
                            dp(out))
+
+
+# ---- triangle counting (tc.hip) ----
+
+def tc_stage_max():
+    """Largest staged-role cap (LDS entries) the kernels accept."""
+    f = lib().lux_gpu_tc_stage_max
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def tc_small_max():
+    """Longest row (oriented arcs) the small role's kernel accepts."""
+    f = lib().lux_gpu_tc_small_max
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def tc_count_items(stream, role, optr, oadj, items, nitems, cap, counters,
+                   pv=None):
+    """Count one role's items (role 0 small, 1 staged, 2 hub) into counters
+    (u64[2]: total, probes) and, with pv (u64[nv], rank-indexed), the
+    per-vertex counts."""
+    rc = lib().lux_gpu_tc_count_items(
+        _u64(stream), ctypes.c_int(role), dp(optr), dp(oadj), dp(items),
+        _u32(nitems), _u32(cap), dp(counters), dp(pv))
+    if rc != 0:
+        raise ValueError(f"tc_count_items: unsupported role={role} / "
+                         f"cap={cap}")
+
+
+def tc_count_plain(stream, nv, m, optr, oadj, counters, pv=None):
+    lib().lux_gpu_tc_count_plain(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                                 dp(oadj), dp(counters), dp(pv))

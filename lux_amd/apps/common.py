@@ -31,6 +31,8 @@ class AppArgs:
         self.delta = 0  # sssp -weighted: bucket width of the bucketed
         #                 (near-far delta-stepping) schedule; 0 = off
         self.nsrc = 1  # bc: number of sources (-start, -start + 1, ...)
+        self.order = "degree"  # tc: vertex order of the orientation
+        #                        (degree | id)
 
 
 def parse_input_args(argv):
@@ -68,6 +70,8 @@ def parse_input_args(argv):
             a.delta = int(argv[i + 1]); i += 2
         elif f == "-nsrc":
             a.nsrc = int(argv[i + 1]); i += 2
+        elif f == "-order":
+            a.order = argv[i + 1]; i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

@@ -74,6 +74,17 @@ def betweenness(g: Graph, source: int):
     return nat.bc_cpu(g.nv, g.ne, g.col_end, g.src, source)
 
 
+def triangles(g: Graph):
+    """Exact triangle counts: (total int, per_vertex u64[nv]) on the
+    underlying simple undirected graph — {u,v} is an edge iff u != v and
+    u->v or v->u occurs, so parallel edges collapse and self-loops vanish
+    (TCEngine's definition). total counts the unordered pairwise-adjacent
+    triples, per_vertex[v] those containing v: per_vertex.sum() == 3*total.
+    C++ node-iterator count on the id-oriented adjacency; shares no code
+    with tc_engine.orient."""
+    return nat.tc_cpu(g.nv, g.ne, g.col_end, g.src)
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

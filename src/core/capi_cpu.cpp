@@ -36,6 +36,8 @@ E_ID sssp_weighted_check(V_ID nv, const E_ID* col_end, const V_ID* src,
                          V_ID source);
 void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
             V_ID source, V_ID* depth, double* sigma, double* delta);
+void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+            uint64_t* total, uint64_t* per_vertex);
 void cf_init(V_ID nv, int K, float* vec);
 void cf_iter_part(V_ID row_left, V_ID row_right, E_ID col_left,
                   const E_ID* col_end, const V_ID* src, const WeightType* w,
@@ -240,6 +242,10 @@ void lux_bc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                 const uint32_t* src, uint32_t source, uint32_t* depth,
                 double* sigma, double* delta) {
   bc_cpu(nv, ne, col_end, src, source, depth, sigma, delta);
+}
+void lux_tc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                const uint32_t* src, uint64_t* total, uint64_t* per_vertex) {
+  tc_cpu(nv, ne, col_end, src, total, per_vertex);
 }
 void lux_cf_init(uint32_t nv, int K, float* vec) { cf_init(nv, K, vec); }
 void lux_cf_iter_part(uint32_t row_left, uint32_t row_right,

@@ -311,6 +311,59 @@ void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   delta[source] = 0.0;
 }
 
+// ---------- Triangle counting ----------
+// Exact oracle of TCEngine (no reference equivalent), on the underlying
+// simple undirected graph: {u,v} is an edge iff u != v and u->v or v->u
+// occurs, so parallel edges collapse and self-loops vanish. Node-iterator
+// counting on the sorted, deduplicated, id-oriented (lo -> hi) adjacency:
+// for every arc u -> v, a merge of A(u) and A(v); each common w is the
+// triangle u < v < w, counted once in *total and once for each corner.
+void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+            uint64_t* total, uint64_t* per_vertex) {
+  std::vector<uint64_t> keys;
+  keys.reserve(ne);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v) continue;
+      V_ID lo = std::min(s, v), hi = std::max(s, v);
+      keys.push_back(((uint64_t)lo << 32) | hi);
+    }
+    b = col_end[v];
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  std::vector<E_ID> ptr((size_t)nv + 1, 0);
+  std::vector<V_ID> adj(keys.size());
+  for (size_t k = 0; k < keys.size(); k++) {
+    ptr[(keys[k] >> 32) + 1]++;
+    adj[k] = (V_ID)(keys[k] & 0xFFFFFFFFu);
+  }
+  for (V_ID v = 0; v < nv; v++) ptr[v + 1] += ptr[v];
+  *total = 0;
+  for (V_ID v = 0; v < nv; v++) per_vertex[v] = 0;
+  for (V_ID u = 0; u < nv; u++) {
+    for (E_ID k = ptr[u]; k < ptr[u + 1]; k++) {
+      V_ID v = adj[k];
+      E_ID i = k + 1, ie = ptr[u + 1];  // A(u) past v: every w is > v
+      E_ID j = ptr[v], je = ptr[v + 1];
+      while (i < ie && j < je) {
+        if (adj[i] < adj[j]) i++;
+        else if (adj[j] < adj[i]) j++;
+        else {
+          (*total)++;
+          per_vertex[u]++;
+          per_vertex[v]++;
+          per_vertex[adj[i]]++;
+          i++;
+          j++;
+        }
+      }
+    }
+  }
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {

@@ -343,4 +343,24 @@ void lux_gpu_bc_check(uint64_t stream, lux::V_ID nv, lux::V_ID source,
                       const float* delta, double rtol,
                       unsigned long long* out);
 
+// tc.hip (triangle counting, single rank)
+// optr u64[nv+1] / oadj u32[m]: the rank-relabelled, lo -> hi oriented
+// simple graph, rows strictly ascending. items: u32 triples {row, first,
+// last} (arc offsets inside the row), one list per role: 0 small (a wave per
+// item, rows of at most small_max arcs; longer ones are skipped), 1 staged (a workgroup per item, the row in cap <= stage_max LDS
+// entries), 2 hub (the same, searched in global memory). counters: u64[2]
+// {total, probes}, added to. pv: u64[nv] rank-indexed per-vertex counts,
+// added to; null counts the total alone.
+uint32_t lux_gpu_tc_stage_max();
+uint32_t lux_gpu_tc_small_max();
+int lux_gpu_tc_count_items(uint64_t stream, int role, const lux::E_ID* optr,
+                           const lux::V_ID* oadj, const uint32_t* items,
+                           uint32_t nitems, uint32_t cap,
+                           unsigned long long* counters,
+                           unsigned long long* pv);
+void lux_gpu_tc_count_plain(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                            const lux::E_ID* optr, const lux::V_ID* oadj,
+                            unsigned long long* counters,
+                            unsigned long long* pv);
+
 }  // extern "C"
