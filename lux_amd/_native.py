@@ -328,3 +328,18 @@ def tc_cpu(nv, ne, col_end, src):
                    ptr(col_end, u64p), ptr(src, u32p), ptr(total, u64p),
                    ptr(per_vertex, u64p))
     return int(total[0]), per_vertex
+
+
+def truss_cpu(nv, ne, col_end, src, want_truss=True):
+    """(edges u32[m, 2] key-sorted, support u32[m], trussness u32[m] or
+    None) of the underlying simple graph."""
+    edges = np.empty((max(ne, 1), 2), np.uint32)
+    support = np.empty(max(ne, 1), np.uint32)
+    truss = np.empty(max(ne, 1), np.uint32) if want_truss else None
+    cpu.lux_truss_cpu.restype = ctypes.c_uint64
+    m = int(cpu.lux_truss_cpu(
+        ctypes.c_uint32(nv), ctypes.c_uint64(ne), ptr(col_end, u64p),
+        ptr(src, u32p), ptr(edges, u32p), ptr(support, u32p),
+        ptr(truss, u32p) if want_truss else None))
+    return (edges[:m].copy(), support[:m].copy(),
+            truss[:m].copy() if want_truss else None)

@@ -85,6 +85,27 @@ def triangles(g: Graph):
     return nat.tc_cpu(g.nv, g.ne, g.col_end, g.src)
 
 
+def edge_support(g: Graph):
+    """(edges u32[m, 2], support u32[m]) on the simple undirected graph of
+    triangles(): edges are (lo, hi) in original ids, sorted by the key
+    (lo << 32) | hi; support[e] is the number of triangles containing e, so
+    support.sum() == 3 * total."""
+    edges, support, _ = nat.truss_cpu(g.nv, g.ne, g.col_end, g.src,
+                                      want_truss=False)
+    return edges, support
+
+
+def truss(g: Graph) -> np.ndarray:
+    """trussness u32[m] in the edge order of edge_support(): the largest k
+    whose k-truss (the largest subgraph whose every edge lies in at least
+    k - 2 triangles of the subgraph) contains the edge; 2 for an edge in no
+    triangle. C++ sequential bucket-queue peeling: remove an edge of
+    minimum support, decrement the other two edges of each of its
+    triangles. Shares no schedule with a round-by-round peel (every round
+    dropping all edges below k - 2), which must give the same answer."""
+    return nat.truss_cpu(g.nv, g.ne, g.col_end, g.src)[2]
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

@@ -14,7 +14,8 @@ underlying simple undirected graph:
                   caller's original vertex ids (a hub's count can pass 2^32);
                   per_vertex.sum() == 3 * total;
   transitivity  = 3 * total / sum_v C(deg(v), 2) with deg the simple
-                  undirected degree; 0.0 when the denominator is 0.
+                  undirected degree; 0.0 when the denominator is 0;
+  clustering[v] = per_vertex[v] / C(deg(v), 2), f64; 0.0 where deg(v) < 2.
 
 Preparation (orient + build_items, torch ops only, one-off): vertices are
 ranked — order="degree": ascending by (simple degree, id); order="id":
@@ -175,6 +176,19 @@ def build_items(optr, stage_cap, t1=TC_T1, chunk=TC_CHUNK):
     return out
 
 
+def clustering(per_vertex, deg):
+    """Local clustering coefficients, f64[nv]: per_vertex / C(deg, 2), the
+    share of a vertex's neighbour pairs that are adjacent; 0 where
+    deg < 2. per_vertex and deg are i64 in the same vertex ids."""
+    pairs = deg * (deg - 1) // 2
+    out = torch.zeros(per_vertex.shape, dtype=torch.float64,
+                      device=per_vertex.device)
+    has = pairs > 0
+    out[has] = per_vertex[has].to(torch.float64) / \
+        pairs[has].to(torch.float64)
+    return out
+
+
 class TCEngine:
     def __init__(self, part: GraphPart, order="degree"):
         if part.nparts != 1:
@@ -264,6 +278,11 @@ class TCEngine:
         deg = self.dag.deg
         wedges = int((deg * (deg - 1) // 2).sum().item())
         return 3 * self._total / wedges if wedges else 0.0
+
+    def clustering(self):
+        """Device f64[nv], original ids: per_vertex / C(deg, 2) with deg the
+        simple undirected degree; 0 where deg < 2."""
+        return clustering(self.per_vertex(), self.dag.deg)
 
     @property
     def stats(self):

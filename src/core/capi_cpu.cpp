@@ -38,6 +38,8 @@ void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
             V_ID source, V_ID* depth, double* sigma, double* delta);
 void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
             uint64_t* total, uint64_t* per_vertex);
+E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+               V_ID* edges, uint32_t* support, uint32_t* trussness);
 void cf_init(V_ID nv, int K, float* vec);
 void cf_iter_part(V_ID row_left, V_ID row_right, E_ID col_left,
                   const E_ID* col_end, const V_ID* src, const WeightType* w,
@@ -246,6 +248,13 @@ void lux_bc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
 void lux_tc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                 const uint32_t* src, uint64_t* total, uint64_t* per_vertex) {
   tc_cpu(nv, ne, col_end, src, total, per_vertex);
+}
+// edges u32[2 * ne], support u32[ne], trussness u32[ne] or null (support
+// only); returns the number of simple edges filled in.
+uint64_t lux_truss_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                       const uint32_t* src, uint32_t* edges,
+                       uint32_t* support, uint32_t* trussness) {
+  return truss_cpu(nv, ne, col_end, src, edges, support, trussness);
 }
 void lux_cf_init(uint32_t nv, int K, float* vec) { cf_init(nv, K, vec); }
 void lux_cf_iter_part(uint32_t row_left, uint32_t row_right,

@@ -364,6 +364,121 @@ void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   }
 }
 
+// ---------- k-truss ----------
+// Exact k-truss oracle (no reference equivalent), on the same simple
+// undirected graph as tc_cpu. Edges are numbered in key order
+// ((lo << 32) | hi, ascending). support[e] = triangles containing e;
+// trussness[e] = the largest k whose k-truss (every edge in >= k - 2
+// triangles inside it) contains e, 2 for an edge in no triangle.
+// Sequential bucket-queue peeling on the full (both directions) adjacency:
+// take an edge of minimum current support s, give it trussness s + 2, and
+// take one off the other two edges of each triangle it still closes. No
+// rounds, no recount, no orientation: nothing in common with a synchronous
+// recompute-per-round peel.
+// edges u32[2 * ne], support u32[ne] and trussness u32[ne] (may be null)
+// are sized for the worst case; the return value m is the number filled.
+E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+               V_ID* edges, uint32_t* support, uint32_t* trussness) {
+  std::vector<uint64_t> keys;
+  keys.reserve(ne);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v) continue;
+      V_ID lo = std::min(s, v), hi = std::max(s, v);
+      keys.push_back(((uint64_t)lo << 32) | hi);
+    }
+    b = col_end[v];
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  const E_ID m = keys.size();
+  // full adjacency with edge ids; scanning the keys in order appends to
+  // every vertex its lower neighbours (ascending) before its higher ones
+  std::vector<E_ID> ptr((size_t)nv + 1, 0);
+  for (E_ID e = 0; e < m; e++) {
+    ptr[(keys[e] >> 32) + 1]++;
+    ptr[(keys[e] & 0xFFFFFFFFu) + 1]++;
+  }
+  for (V_ID v = 0; v < nv; v++) ptr[v + 1] += ptr[v];
+  std::vector<V_ID> nbr(2 * m);
+  std::vector<E_ID> eid(2 * m);
+  {
+    std::vector<E_ID> fill(ptr.begin(), ptr.end() - 1);
+    for (E_ID e = 0; e < m; e++) {
+      V_ID lo = (V_ID)(keys[e] >> 32), hi = (V_ID)(keys[e] & 0xFFFFFFFFu);
+      edges[2 * e] = lo;
+      edges[2 * e + 1] = hi;
+      nbr[fill[lo]] = hi;
+      eid[fill[lo]++] = e;
+      nbr[fill[hi]] = lo;
+      eid[fill[hi]++] = e;
+    }
+  }
+  // calls f(e1, e2) with the edges (lo, w), (hi, w) of every common
+  // neighbour w of edge e's endpoints
+  auto triangles_of = [&](E_ID e, auto&& f) {
+    V_ID lo = edges[2 * e], hi = edges[2 * e + 1];
+    E_ID i = ptr[lo], ie = ptr[lo + 1], j = ptr[hi], je = ptr[hi + 1];
+    while (i < ie && j < je) {
+      if (nbr[i] < nbr[j]) i++;
+      else if (nbr[j] < nbr[i]) j++;
+      else {
+        f(eid[i], eid[j]);
+        i++;
+        j++;
+      }
+    }
+  };
+  uint32_t smax = 0;
+  for (E_ID e = 0; e < m; e++) {
+    uint32_t s = 0;
+    triangles_of(e, [&](E_ID, E_ID) { s++; });
+    support[e] = s;
+    smax = std::max(smax, s);
+  }
+  if (!trussness || !m) return m;
+  // bucket queue: order holds the edges ascending by current support,
+  // bin[s] is where the edges of support s start, pos the inverse of order
+  std::vector<uint32_t> cur(support, support + m);
+  std::vector<E_ID> bin((size_t)smax + 2, 0), order(m), pos(m);
+  for (E_ID e = 0; e < m; e++) bin[cur[e] + 1]++;
+  for (uint32_t s = 0; s <= smax; s++) bin[s + 1] += bin[s];
+  {
+    std::vector<E_ID> fill(bin.begin(), bin.end() - 1);
+    for (E_ID e = 0; e < m; e++) {
+      pos[e] = fill[cur[e]]++;
+      order[pos[e]] = e;
+    }
+  }
+  std::vector<char> gone(m, 0);
+  for (E_ID k = 0; k < m; k++) {
+    E_ID e = order[k];
+    uint32_t s = cur[e];
+    trussness[e] = s + 2;
+    gone[e] = 1;
+    triangles_of(e, [&](E_ID e1, E_ID e2) {
+      if (gone[e1] || gone[e2]) return;
+      for (E_ID f : {e1, e2}) {
+        if (cur[f] <= s) continue;
+        // swap f with the first edge of its bin, then shrink the bin
+        E_ID pf = pos[f], pw = std::max(bin[cur[f]], k + 1);
+        E_ID w = order[pw];
+        if (w != f) {
+          order[pf] = w;
+          pos[w] = pf;
+          order[pw] = f;
+          pos[f] = pw;
+        }
+        bin[cur[f]] = pw + 1;
+        cur[f]--;
+      }
+    });
+  }
+  return m;
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {
