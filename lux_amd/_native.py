@@ -343,3 +343,12 @@ def truss_cpu(nv, ne, col_end, src, want_truss=True):
         ptr(truss, u32p) if want_truss else None))
     return (edges[:m].copy(), support[:m].copy(),
             truss[:m].copy() if want_truss else None)
+
+
+def coreness_cpu(nv, ne, col_end, src):
+    """coreness u32[nv] of the underlying simple graph."""
+    core = np.empty(nv, np.uint32)
+    cpu.lux_coreness_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                         ptr(col_end, u64p), ptr(src, u32p),
+                         ptr(core, u32p))
+    return core

@@ -532,3 +532,71 @@ def tc_count_items(stream, role, optr, oadj, items, nitems, cap, counters,
 def tc_count_plain(stream, nv, m, optr, oadj, counters, pv=None):
     lib().lux_gpu_tc_count_plain(_u64(stream), _u32(nv), _u64(m), dp(optr),
                                  dp(oadj), dp(counters), dp(pv))
+
+
+# ---- k-core decomposition (kcore.hip) ----
+
+def _kcore_const(name):
+    f = getattr(lib(), name)
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def kcore_hub_default():
+    """KCORE_HUB: the longest row the row role takes when LUX_KCORE_HUB is
+    unset."""
+    return _kcore_const("lux_gpu_kcore_hub_default")
+
+
+def kcore_fuse_default():
+    """KCORE_FUSE: the tail kernel's round size when LUX_KCORE_FUSE is
+    unset."""
+    return _kcore_const("lux_gpu_kcore_fuse_default")
+
+
+def kcore_fuse_max():
+    return _kcore_const("lux_gpu_kcore_fuse_max")
+
+
+def kcore_meta_words():
+    return _kcore_const("lux_gpu_kcore_meta_words")
+
+
+def kcore_adj_fill(stream, nv, m, optr, oadj, aptr, cursor, aadj):
+    lib().lux_gpu_kcore_adj_fill(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                                 dp(oadj), dp(aptr), dp(cursor), dp(aadj))
+
+
+def kcore_scan(stream, nv, aptr, deg, order, hubq, hubcap, meta, hub, k):
+    lib().lux_gpu_kcore_scan(_u64(stream), _u32(nv), dp(aptr), dp(deg),
+                             dp(order), dp(hubq), _u32(hubcap), dp(meta),
+                             _u32(hub), ctypes.c_int(k))
+
+
+def kcore_peel(stream, nv, aptr, aadj, deg, order, hubq, hubcap, meta, hub,
+               k, head, tail, hubhead, hubtail):
+    """One round: order[head:tail) and the hubq items [hubhead, hubtail)."""
+    rc = lib().lux_gpu_kcore_peel(
+        _u64(stream), _u32(nv), dp(aptr), dp(aadj), dp(deg), dp(order),
+        dp(hubq), _u32(hubcap), dp(meta), _u32(hub), ctypes.c_int(k),
+        _u32(head), _u32(tail), _u32(hubhead), _u32(hubtail))
+    if rc != 0:
+        raise ValueError(f"kcore_peel: bad round [{head}, {tail}) / "
+                         f"[{hubhead}, {hubtail}), hub={hub}")
+
+
+def kcore_tail(stream, nv, aptr, aadj, deg, order, hubq, hubcap, meta, hub,
+               k, head, tail, hubtail, fuse):
+    """Small rounds of the level from order[head:tail) on, one workgroup."""
+    rc = lib().lux_gpu_kcore_tail(
+        _u64(stream), _u32(nv), dp(aptr), dp(aadj), dp(deg), dp(order),
+        dp(hubq), _u32(hubcap), dp(meta), _u32(hub), ctypes.c_int(k),
+        _u32(head), _u32(tail), _u32(hubtail), _u32(fuse))
+    if rc != 0:
+        raise ValueError(f"kcore_tail: round [{head}, {tail}) does not "
+                         f"qualify (fuse={fuse}, hub={hub})")
+
+
+def kcore_check(stream, nv, aptr, aadj, core, bad):
+    lib().lux_gpu_kcore_check(_u64(stream), _u32(nv), dp(aptr), dp(aadj),
+                              dp(core), dp(bad))

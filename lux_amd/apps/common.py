@@ -33,6 +33,7 @@ class AppArgs:
         self.nsrc = 1  # bc: number of sources (-start, -start + 1, ...)
         self.order = "degree"  # tc: vertex order of the orientation
         #                        (degree | id)
+        self.kcore = None  # kcore: also report the size of this K-core
 
 
 def parse_input_args(argv):
@@ -72,6 +73,8 @@ def parse_input_args(argv):
             a.nsrc = int(argv[i + 1]); i += 2
         elif f == "-order":
             a.order = argv[i + 1]; i += 2
+        elif f == "-kcore":
+            a.kcore = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

@@ -106,6 +106,16 @@ def truss(g: Graph) -> np.ndarray:
     return nat.truss_cpu(g.nv, g.ne, g.col_end, g.src)[2]
 
 
+def coreness(g: Graph) -> np.ndarray:
+    """coreness u32[nv] on the simple undirected graph of triangles(): the
+    largest k whose k-core (the largest subgraph in which every vertex has
+    degree >= k) contains the vertex; 0 for a vertex with no simple edge.
+    coreness.max() is the degeneracy. C++ sequential Batagelj-Zaversnik
+    bucket peel, O(m); shares no code with tc_engine.orient and no schedule
+    with KCoreEngine's round-by-round peel."""
+    return nat.coreness_cpu(g.nv, g.ne, g.col_end, g.src)
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

@@ -479,6 +479,82 @@ E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   return m;
 }
 
+// ---------- k-core ----------
+// Exact coreness oracle of KCoreEngine (no reference equivalent), on the
+// same simple undirected graph as tc_cpu. coreness[v] = the largest k whose
+// k-core (the largest subgraph in which every vertex has degree >= k)
+// contains v; 0 for a vertex with no simple edge. Sequential
+// Batagelj-Zaversnik bucket peel, O(m): vert holds the vertices ascending
+// by current degree, bin[d] is where degree d starts, pos the inverse of
+// vert; take the next vertex, fix its coreness at its current degree and
+// move every neighbour of larger degree one bin down. No rounds, no queue.
+void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+                  uint32_t* coreness) {
+  std::vector<uint64_t> keys;
+  keys.reserve(ne);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v) continue;
+      V_ID lo = std::min(s, v), hi = std::max(s, v);
+      keys.push_back(((uint64_t)lo << 32) | hi);
+    }
+    b = col_end[v];
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  const E_ID m = keys.size();
+  std::vector<E_ID> ptr((size_t)nv + 1, 0);
+  for (E_ID e = 0; e < m; e++) {
+    ptr[(keys[e] >> 32) + 1]++;
+    ptr[(keys[e] & 0xFFFFFFFFu) + 1]++;
+  }
+  for (V_ID v = 0; v < nv; v++) ptr[v + 1] += ptr[v];
+  std::vector<V_ID> nbr(2 * m);
+  {
+    std::vector<E_ID> fill(ptr.begin(), ptr.end() - 1);
+    for (E_ID e = 0; e < m; e++) {
+      V_ID lo = (V_ID)(keys[e] >> 32), hi = (V_ID)(keys[e] & 0xFFFFFFFFu);
+      nbr[fill[lo]++] = hi;
+      nbr[fill[hi]++] = lo;
+    }
+  }
+  uint32_t dmax = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    coreness[v] = (uint32_t)(ptr[v + 1] - ptr[v]);  // the current degree
+    dmax = std::max(dmax, coreness[v]);
+  }
+  std::vector<V_ID> bin((size_t)dmax + 2, 0), vert(nv), pos(nv);
+  for (V_ID v = 0; v < nv; v++) bin[coreness[v] + 1]++;
+  for (uint32_t d = 0; d <= dmax; d++) bin[d + 1] += bin[d];
+  {
+    std::vector<V_ID> fill(bin.begin(), bin.end() - 1);
+    for (V_ID v = 0; v < nv; v++) {
+      pos[v] = fill[coreness[v]]++;
+      vert[pos[v]] = v;
+    }
+  }
+  for (V_ID k = 0; k < nv; k++) {
+    V_ID v = vert[k];
+    for (E_ID i = ptr[v]; i < ptr[v + 1]; i++) {
+      V_ID u = nbr[i];
+      if (coreness[u] <= coreness[v]) continue;
+      // swap u with the first vertex of its bin, then shrink the bin
+      V_ID pu = pos[u], pw = bin[coreness[u]];
+      V_ID w = vert[pw];
+      if (w != u) {
+        vert[pu] = w;
+        pos[w] = pu;
+        vert[pw] = u;
+        pos[u] = pw;
+      }
+      bin[coreness[u]]++;
+      coreness[u]--;
+    }
+  }
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {

@@ -363,4 +363,39 @@ void lux_gpu_tc_count_plain(uint64_t stream, lux::V_ID nv, lux::E_ID m,
                             unsigned long long* counters,
                             unsigned long long* pv);
 
+// kcore.hip (k-core decomposition by synchronous peeling, single rank)
+// optr u64[nv+1] / oadj u32[m]: the id-order DAG of the simple graph (row u
+// lists its neighbours > u). aptr u64[nv+1] / aadj u32[2m]: the full
+// symmetric adjacency. deg i32[nv]: the current degree, the coreness at the
+// end. order u32[nv] and hubq ({vertex, chunk} u32 pairs, hubcap of them):
+// append-only lists, a round being order[head : tail) plus
+// hubq[hubhead : hubtail). meta u32[meta_words]: [0] the order cursor, [1]
+// the hubq cursor, [2] the scan's min{deg : deg > k} (0xFFFFFFFF: none),
+// [3] rounds done and [4] first unprocessed entry of the last tail launch.
+// hub: rows longer than this are peeled by hubq chunks of hub entries.
+uint32_t lux_gpu_kcore_hub_default();
+uint32_t lux_gpu_kcore_fuse_default();
+uint32_t lux_gpu_kcore_fuse_max();
+uint32_t lux_gpu_kcore_meta_words();
+void lux_gpu_kcore_adj_fill(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                            const lux::E_ID* optr, const lux::V_ID* oadj,
+                            const lux::E_ID* aptr, uint32_t* cursor,
+                            lux::V_ID* aadj);
+void lux_gpu_kcore_scan(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
+                        int* deg, lux::V_ID* order, uint32_t* hubq,
+                        uint32_t hubcap, uint32_t* meta, uint32_t hub, int k);
+int lux_gpu_kcore_peel(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
+                       const lux::V_ID* aadj, int* deg, lux::V_ID* order,
+                       uint32_t* hubq, uint32_t hubcap, uint32_t* meta,
+                       uint32_t hub, int k, uint32_t head, uint32_t tail,
+                       uint32_t hubhead, uint32_t hubtail);
+int lux_gpu_kcore_tail(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
+                       const lux::V_ID* aadj, int* deg, lux::V_ID* order,
+                       uint32_t* hubq, uint32_t hubcap, uint32_t* meta,
+                       uint32_t hub, int k, uint32_t head, uint32_t tail,
+                       uint32_t hubtail, uint32_t fuse);
+void lux_gpu_kcore_check(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
+                         const lux::V_ID* aadj, const int* core,
+                         unsigned long long* bad);
+
 }  // extern "C"
