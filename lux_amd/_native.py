@@ -352,3 +352,11 @@ def coreness_cpu(nv, ne, col_end, src):
                          ptr(col_end, u64p), ptr(src, u32p),
                          ptr(core, u32p))
     return core
+
+
+def scc_cpu(nv, ne, col_end, src):
+    """label u32[nv]: the largest vertex id of each vertex's SCC."""
+    label = np.empty(nv, np.uint32)
+    cpu.lux_scc_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                    ptr(col_end, u64p), ptr(src, u32p), ptr(label, u32p))
+    return label

@@ -600,3 +600,132 @@ def kcore_tail(stream, nv, aptr, aadj, deg, order, hubq, hubcap, meta, hub,
 def kcore_check(stream, nv, aptr, aadj, core, bad):
     lib().lux_gpu_kcore_check(_u64(stream), _u32(nv), dp(aptr), dp(aadj),
                               dp(core), dp(bad))
+
+
+# ---- strongly connected components (scc.hip) ----
+
+class SccArgs(ctypes.Structure):
+    """lux_scc_args: the graph in both directions and the per-vertex state."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "in_ptr", "in_col", "out_ptr", "out_col", "label", "in_cnt",
+        "out_cnt", "colour", "mark", "stamp", "hubq", "meta")] + \
+        [("nv", ctypes.c_uint32), ("hub", ctypes.c_uint32)]
+
+
+class SccStep(ctypes.Structure):
+    """lux_scc_step: one frontier step or trim round."""
+    _fields_ = [("qr", ctypes.c_void_p), ("qw", ctypes.c_void_p)] + \
+        [(n, ctypes.c_uint32) for n in ("qcap", "mw", "hr0", "hw0", "hcap")] + \
+        [(n, ctypes.c_int) for n in ("mode", "dir", "cmode")] + \
+        [("bit", ctypes.c_uint32), ("step", ctypes.c_uint32)]
+
+
+SCC_TRIM, SCC_REACH, SCC_COLOUR = 0, 1, 2
+SCC_F, SCC_B = 1, 2
+# meta words
+(SCC_M_TTAIL, SCC_M_RTAIL, SCC_M_CTAIL, SCC_M_HUBTAIL, SCC_M_FUSED,
+ SCC_M_HEAD, SCC_M_DIED, SCC_M_MAXID, SCC_M_PIVOT) = range(9)
+
+
+def _scc_const(name):
+    f = getattr(lib(), name)
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def scc_hub_default():
+    """SCC_HUB: the longest row the row role takes when LUX_SCC_HUB is
+    unset."""
+    return _scc_const("lux_gpu_scc_hub_default")
+
+
+def scc_fuse_default():
+    """SCC_FUSE: the tail kernel's step size when LUX_SCC_FUSE is unset."""
+    return _scc_const("lux_gpu_scc_fuse_default")
+
+
+def scc_fuse_max():
+    return _scc_const("lux_gpu_scc_fuse_max")
+
+
+def scc_meta_words():
+    return _scc_const("lux_gpu_scc_meta_words")
+
+
+def scc_args(in_ptr, in_col, out_ptr, out_col, label, in_cnt, out_cnt,
+             colour, mark, stamp, hubq, meta, nv, hub):
+    return SccArgs(*(t.data_ptr() for t in (
+        in_ptr, in_col, out_ptr, out_col, label, in_cnt, out_cnt, colour,
+        mark, stamp, hubq, meta)), nv, hub)
+
+
+def scc_step_desc(qr, qw, qcap, mw, hcap, mode, hr0=0, hw0=0, dir=0, cmode=0,
+                  bit=0, step=0):
+    """qr / qw: raw device addresses of the read and the write queue."""
+    return SccStep(qr, qw, qcap, mw, hr0, hw0, hcap, mode, dir, cmode, bit,
+                   step)
+
+
+def scc_count(stream, a, st, items, nitems):
+    """items: the static {vertex, chunk} list of the rows longer than hub."""
+    lib().lux_gpu_scc_count(_u64(stream), ctypes.byref(a), ctypes.byref(st),
+                            dp(items), _u32(nitems))
+
+
+def scc_pivot(stream, a):
+    lib().lux_gpu_scc_pivot(_u64(stream), ctypes.byref(a))
+
+
+def scc_scan(stream, a, st, what):
+    """what 0: colour = id and the first colour frontier; 1: the roots."""
+    lib().lux_gpu_scc_scan(_u64(stream), ctypes.byref(a), ctypes.byref(st),
+                           ctypes.c_int(what))
+
+
+def scc_seed(stream, a, st, v, restart):
+    lib().lux_gpu_scc_seed(_u64(stream), ctypes.byref(a), ctypes.byref(st),
+                           _u32(v), ctypes.c_int(restart))
+
+
+def scc_step(stream, a, st, head, tail, hubhead, hubtail, restart=0):
+    """One step: st.qr[head:tail) and the hubq items [hubhead, hubtail)."""
+    rc = lib().lux_gpu_scc_step(
+        _u64(stream), ctypes.byref(a), ctypes.byref(st), _u32(head),
+        _u32(tail), _u32(hubhead), _u32(hubtail), ctypes.c_int(restart))
+    if rc != 0:
+        raise ValueError(f"scc_step: bad step [{head}, {tail}) / "
+                         f"[{hubhead}, {hubtail}), mode={st.mode}")
+
+
+def scc_tail(stream, a, st, head, tail, hubtail, fuse, pingpong=0):
+    """Small steps from st.qr[head:tail) on, one workgroup."""
+    rc = lib().lux_gpu_scc_tail(
+        _u64(stream), ctypes.byref(a), ctypes.byref(st), _u32(head),
+        _u32(tail), _u32(hubtail), _u32(fuse), ctypes.c_int(pingpong))
+    if rc != 0:
+        raise ValueError(f"scc_tail: step [{head}, {tail}) does not qualify "
+                         f"(fuse={fuse}, mode={st.mode})")
+
+
+def scc_commit(stream, a, colour):
+    lib().lux_gpu_scc_commit(_u64(stream), ctypes.byref(a),
+                             ctypes.c_int(colour))
+
+
+def scc_check_vertex(stream, nv, label, fwd, bwd, bad, what):
+    lib().lux_gpu_scc_check_vertex(_u64(stream), _u32(nv), dp(label), dp(fwd),
+                                   dp(bwd), dp(bad), ctypes.c_int(what))
+
+
+def scc_check_sweep(stream, nv, in_ptr, in_col, out_ptr, out_col, label, fwd,
+                    bwd, changed):
+    lib().lux_gpu_scc_check_sweep(_u64(stream), _u32(nv), dp(in_ptr),
+                                  dp(in_col), dp(out_ptr), dp(out_col),
+                                  dp(label), dp(fwd), dp(bwd), dp(changed))
+
+
+def scc_check_pairs(stream, nv, ne, in_ptr, in_col, out_ptr, out_col, label,
+                    bad):
+    lib().lux_gpu_scc_check_pairs(_u64(stream), _u32(nv), _u64(ne),
+                                  dp(in_ptr), dp(in_col), dp(out_ptr),
+                                  dp(out_col), dp(label), dp(bad))

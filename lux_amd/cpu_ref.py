@@ -116,6 +116,17 @@ def coreness(g: Graph) -> np.ndarray:
     return nat.coreness_cpu(g.nv, g.ne, g.col_end, g.src)
 
 
+def scc(g: Graph) -> np.ndarray:
+    """label u32[nv] of the directed graph as loaded (row v of the CSC lists
+    the sources u of the edges u -> v; parallel edges and self-loops change
+    nothing): u and v share a label iff each reaches the other, and the
+    label is the largest vertex id of the SCC, so label[v] >= v,
+    label[label[v]] == label[v], and a vertex alone in its SCC has
+    label[v] == v. C++ iterative Tarjan (an explicit call stack); shares no
+    schedule with SCCEngine's trim / forward-backward / colouring."""
+    return nat.scc_cpu(g.nv, g.ne, g.col_end, g.src)
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

@@ -42,6 +42,8 @@ E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                V_ID* edges, uint32_t* support, uint32_t* trussness);
 void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                   uint32_t* coreness);
+void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+             uint32_t* label);
 void cf_init(V_ID nv, int K, float* vec);
 void cf_iter_part(V_ID row_left, V_ID row_right, E_ID col_left,
                   const E_ID* col_end, const V_ID* src, const WeightType* w,
@@ -261,6 +263,10 @@ uint64_t lux_truss_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
 void lux_coreness_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                       const uint32_t* src, uint32_t* coreness) {
   coreness_cpu(nv, ne, col_end, src, coreness);
+}
+void lux_scc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                 const uint32_t* src, uint32_t* label) {
+  scc_cpu(nv, ne, col_end, src, label);
 }
 void lux_cf_init(uint32_t nv, int K, float* vec) { cf_init(nv, K, vec); }
 void lux_cf_iter_part(uint32_t row_left, uint32_t row_right,

@@ -555,6 +555,67 @@ void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   }
 }
 
+// ---------- strongly connected components ----------
+// Exact oracle of SCCEngine (no reference equivalent), on the directed graph
+// as loaded: row v of the CSC lists the sources u of the edges u -> v.
+// label[v] = the largest vertex id of v's SCC. Tarjan's algorithm with an
+// explicit call stack (no recursion: a path of thousands of vertices is a
+// test). The search walks the CSC rows, i.e. the reversed graph, whose SCCs
+// are the same. No trim, no pivot, no colouring.
+void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+             uint32_t* label) {
+  (void)ne;
+  constexpr uint32_t UNSEEN = 0xFFFFFFFFu;
+  std::vector<uint32_t> index(nv, UNSEEN), low(nv, 0);
+  std::vector<uint8_t> on_stack(nv, 0);
+  std::vector<V_ID> stack, call;
+  std::vector<E_ID> next(nv, 0);  // the next in-edge of a vertex on `call`
+  uint32_t counter = 0;
+  for (V_ID root = 0; root < nv; root++) {
+    if (index[root] != UNSEEN) continue;
+    call.push_back(root);
+    while (!call.empty()) {
+      V_ID v = call.back();
+      if (index[v] == UNSEEN) {
+        index[v] = low[v] = counter++;
+        stack.push_back(v);
+        on_stack[v] = 1;
+        next[v] = v == 0 ? 0 : col_end[v - 1];
+      }
+      bool descended = false;
+      while (next[v] < col_end[v]) {
+        V_ID u = src[next[v]++];
+        if (u >= nv) continue;
+        if (index[u] == UNSEEN) {
+          call.push_back(u);
+          descended = true;
+          break;
+        }
+        if (on_stack[u]) low[v] = std::min(low[v], index[u]);
+      }
+      if (descended) continue;
+      call.pop_back();
+      if (!call.empty()) {
+        V_ID p = call.back();
+        low[p] = std::min(low[p], low[v]);
+      }
+      if (low[v] != index[v]) continue;
+      // v is the root of a component: the stack down to v
+      size_t first = stack.size();
+      V_ID top = 0;
+      do {
+        first--;
+        top = std::max(top, stack[first]);
+      } while (stack[first] != v);
+      for (size_t i = first; i < stack.size(); i++) {
+        label[stack[i]] = top;
+        on_stack[stack[i]] = 0;
+      }
+      stack.resize(first);
+    }
+  }
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {

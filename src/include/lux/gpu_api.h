@@ -398,4 +398,73 @@ void lux_gpu_kcore_check(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
                          const lux::V_ID* aadj, const int* core,
                          unsigned long long* bad);
 
+// scc.hip (strongly connected components: trim, forward-backward reach and
+// colour propagation; single rank). lux_scc_args is the graph in both
+// directions and the per-vertex state, lux_scc_step one frontier step or
+// trim round: it reads qr[head : tail) and the hubq items
+// [hr0 + hubhead, hr0 + hubtail), appends to qw at the cursor meta[mw]
+// (below qcap) and to hubq from hw0 at the cursor meta[3] (below hcap).
+// mode 0 trim / 1 reach / 2 colour; dir 0 along out-edges, 1 along in-edges;
+// cmode: reach only inside the frontier vertex's colour; bit: the mark bit
+// of the traversal; step: the colour step's stamp. meta u32[meta_words]:
+// [0] trim, [1] reach, [2] colour queue cursors, [3] the hubq cursor, [4]
+// steps done and [5] first unprocessed entry of the last tail launch, [6]
+// died and [7] max id of the last commit, [8] the pivot.
+struct lux_scc_args {
+  const lux::E_ID* in_ptr;   // u64[nv+1]
+  const lux::V_ID* in_col;   // u32[ne]
+  const lux::E_ID* out_ptr;  // u64[nv+1]
+  const lux::V_ID* out_col;  // u32[ne]
+  uint32_t* label;           // u32[nv], 0xFFFFFFFF = alive
+  int* in_cnt;               // i32[nv]
+  int* out_cnt;              // i32[nv]
+  uint32_t* colour;          // u32[nv]
+  uint32_t* mark;            // u32[nv]
+  uint32_t* stamp;           // u32[nv]
+  uint32_t* hubq;            // u32 pairs
+  uint32_t* meta;            // u32[meta_words]
+  lux::V_ID nv;
+  uint32_t hub;  // rows longer than this go through hubq
+};
+struct lux_scc_step {
+  const lux::V_ID* qr;
+  lux::V_ID* qw;
+  uint32_t qcap, mw, hr0, hw0, hcap;
+  int mode, dir, cmode;
+  uint32_t bit, step;
+};
+uint32_t lux_gpu_scc_hub_default();
+uint32_t lux_gpu_scc_fuse_default();
+uint32_t lux_gpu_scc_fuse_max();
+uint32_t lux_gpu_scc_meta_words();
+void lux_gpu_scc_count(uint64_t stream, const lux_scc_args* a,
+                       const lux_scc_step* st, const uint32_t* items,
+                       uint32_t nitems);
+void lux_gpu_scc_pivot(uint64_t stream, const lux_scc_args* a);
+void lux_gpu_scc_scan(uint64_t stream, const lux_scc_args* a,
+                      const lux_scc_step* st, int what);
+void lux_gpu_scc_seed(uint64_t stream, const lux_scc_args* a,
+                      const lux_scc_step* st, lux::V_ID v, int restart);
+int lux_gpu_scc_step(uint64_t stream, const lux_scc_args* a,
+                     const lux_scc_step* st, uint32_t head, uint32_t tail,
+                     uint32_t hubhead, uint32_t hubtail, int restart);
+int lux_gpu_scc_tail(uint64_t stream, const lux_scc_args* a,
+                     const lux_scc_step* st, uint32_t head, uint32_t tail,
+                     uint32_t hubtail, uint32_t fuse, int pingpong);
+void lux_gpu_scc_commit(uint64_t stream, const lux_scc_args* a, int colour);
+void lux_gpu_scc_check_vertex(uint64_t stream, lux::V_ID nv,
+                              const uint32_t* label, uint32_t* fwd,
+                              uint32_t* bwd, unsigned long long* bad,
+                              int what);
+void lux_gpu_scc_check_sweep(uint64_t stream, lux::V_ID nv,
+                             const lux::E_ID* in_ptr, const lux::V_ID* in_col,
+                             const lux::E_ID* out_ptr,
+                             const lux::V_ID* out_col, const uint32_t* label,
+                             uint32_t* fwd, uint32_t* bwd, uint32_t* changed);
+void lux_gpu_scc_check_pairs(uint64_t stream, lux::V_ID nv, lux::E_ID ne,
+                             const lux::E_ID* in_ptr, const lux::V_ID* in_col,
+                             const lux::E_ID* out_ptr,
+                             const lux::V_ID* out_col, const uint32_t* label,
+                             unsigned long long* bad);
+
 }  // extern "C"
