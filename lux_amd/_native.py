@@ -360,3 +360,23 @@ def scc_cpu(nv, ne, col_end, src):
     cpu.lux_scc_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
                     ptr(col_end, u64p), ptr(src, u32p), ptr(label, u32p))
     return label
+
+
+def msf_cpu(nv, ne, col_end, src, weight):
+    """(lo u32[m], hi u32[m], w i32[m], in_forest bool[m], total int,
+    label u32[nv]) of the underlying simple graph, edges in key order."""
+    n1 = max(ne, 1)
+    lo = np.empty(n1, np.uint32)
+    hi = np.empty(n1, np.uint32)
+    w = np.empty(n1, np.int32)
+    mark = np.empty(n1, np.uint8)
+    total = np.zeros(1, np.int64)
+    label = np.empty(nv, np.uint32)
+    cpu.lux_msf_cpu.restype = ctypes.c_uint64
+    m = int(cpu.lux_msf_cpu(
+        ctypes.c_uint32(nv), ctypes.c_uint64(ne), ptr(col_end, u64p),
+        ptr(src, u32p), ptr(weight, i32p), ptr(lo, u32p), ptr(hi, u32p),
+        ptr(w, i32p), ptr(mark, ctypes.POINTER(ctypes.c_uint8)),
+        ptr(total, ctypes.POINTER(ctypes.c_int64)), ptr(label, u32p)))
+    return (lo[:m].copy(), hi[:m].copy(), w[:m].copy(),
+            mark[:m].astype(np.bool_), int(total[0]), label)

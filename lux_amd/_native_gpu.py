@@ -729,3 +729,104 @@ def scc_check_pairs(stream, nv, ne, in_ptr, in_col, out_ptr, out_col, label,
     lib().lux_gpu_scc_check_pairs(_u64(stream), _u32(nv), _u64(ne),
                                   dp(in_ptr), dp(in_col), dp(out_ptr),
                                   dp(out_col), dp(label), dp(bad))
+
+
+# ---- minimum spanning forest (msf.hip) ----
+
+class MsfArgs(ctypes.Structure):
+    """lux_msf_args: the adjacency with edge ids, the simple edges, the
+    static hub items and the state of a solve."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "aptr", "anbr", "aeid", "elo", "ehi", "w", "comp", "parent", "best",
+        "dead", "inforest", "hubrow", "hubext", "item_row", "item_chunk",
+        "meta")] + \
+        [("m", ctypes.c_uint64), ("nv", ctypes.c_uint32),
+         ("nhub", ctypes.c_uint32), ("nitems", ctypes.c_uint32),
+         ("hub", ctypes.c_uint32), ("use_dead", ctypes.c_int)]
+
+
+# meta words
+(MSF_M_CWE, MSF_M_MERGED, MSF_M_SCANNED, MSF_M_TOTAL, MSF_M_NF,
+ MSF_M_ERR) = range(6)
+
+
+def _msf_const(name):
+    f = getattr(lib(), name)
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def msf_hub_default():
+    """MSF_HUB: the longest row the row role takes when LUX_MSF_HUB is
+    unset."""
+    return _msf_const("lux_gpu_msf_hub_default")
+
+
+def msf_meta_words():
+    return _msf_const("lux_gpu_msf_meta_words")
+
+
+def msf_args(aptr, anbr, aeid, elo, ehi, w, comp, parent, best, dead,
+             inforest, hubrow, hubext, item_row, item_chunk, meta, m, nv,
+             nhub, nitems, hub, use_dead):
+    return MsfArgs(*(t.data_ptr() for t in (
+        aptr, anbr, aeid, elo, ehi, w, comp, parent, best, dead, inforest,
+        hubrow, hubext, item_row, item_chunk, meta)), m, nv, nhub, nitems,
+        hub, int(bool(use_dead)))
+
+
+def msf_weights(stream, nv, ne, row_ptr, col, weight, optr, oadj, w, err):
+    """w (preset to INT32_MAX)[e] = the minimum weight over the CSC arcs of
+    simple edge e; err counts arcs whose edge the DAG does not hold."""
+    lib().lux_gpu_msf_weights(_u64(stream), _u32(nv), _u64(ne), dp(row_ptr),
+                              dp(col), dp(weight), dp(optr), dp(oadj), dp(w),
+                              dp(err))
+
+
+def msf_adj_fill(stream, nv, m, optr, oadj, aptr, cursor, anbr, aeid, elo):
+    lib().lux_gpu_msf_adj_fill(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                               dp(oadj), dp(aptr), dp(cursor), dp(anbr),
+                               dp(aeid), dp(elo))
+
+
+def msf_init(stream, a):
+    lib().lux_gpu_msf_init(_u64(stream), ctypes.byref(a))
+
+
+def msf_scan(stream, a, stamp):
+    """Scan number stamp (1, 2, ...); returns the kernels launched."""
+    rc = lib().lux_gpu_msf_scan(_u64(stream), ctypes.byref(a), _u32(stamp))
+    if rc < 0:
+        raise ValueError(f"msf_scan: bad arguments (stamp={stamp}, "
+                         f"hub={a.hub}, m={a.m})")
+    return rc
+
+
+def msf_hook(stream, a):
+    lib().lux_gpu_msf_hook(_u64(stream), ctypes.byref(a))
+
+
+def msf_flatten(stream, a):
+    lib().lux_gpu_msf_flatten(_u64(stream), ctypes.byref(a))
+
+
+def msf_labels(stream, nv, comp, maxid, labels):
+    lib().lux_gpu_msf_labels(_u64(stream), _u32(nv), dp(comp), dp(maxid),
+                             dp(labels))
+
+
+def msf_check(stream, nv, m, aptr, aeid, elo, ehi, w, mask, labels, pf, pa,
+              out):
+    """out u64[4]: violations, marked edges, vertices with label == id, the
+    marked edges' weight."""
+    lib().lux_gpu_msf_check(_u64(stream), _u32(nv), _u64(m), dp(aptr),
+                            dp(aeid), dp(elo), dp(ehi), dp(w), dp(mask),
+                            dp(labels), dp(pf), dp(pa), dp(out))
+
+
+def msf_set_mark(stream, mask, m, e, value):
+    """mask[e] = value on a u8[m] forest mask (the tests' corruption)."""
+    rc = lib().lux_gpu_msf_set_mark(_u64(stream), dp(mask), _u64(m), _u64(e),
+                                    ctypes.c_int(value))
+    if rc != 0:
+        raise ValueError(f"msf_set_mark: edge {e} outside [0, {m})")

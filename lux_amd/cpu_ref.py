@@ -127,6 +127,22 @@ def scc(g: Graph) -> np.ndarray:
     return nat.scc_cpu(g.nv, g.ne, g.col_end, g.src)
 
 
+def msf(g: Graph):
+    """The minimum spanning forest of the simple undirected graph of
+    triangles(), the weight of {u, v} being the minimum of g.weight over all
+    its occurrences in either direction (any i32). Returns (lo u32[m],
+    hi u32[m], w i32[m], in_forest bool[m], total int, labels u32[nv]): the
+    simple edges ascending by (lo << 32) | hi — the position is the edge id
+    e — the forest under the strict order (w, e), its exact total weight,
+    and per vertex the largest vertex id of its component. C++ Kruskal over
+    its own sorted edge list; shares no code with tc_engine.orient and no
+    schedule with MSFEngine's Boruvka rounds."""
+    if g.weight is None:
+        raise ValueError("msf needs g.weight")
+    return nat.msf_cpu(g.nv, g.ne, g.col_end, g.src,
+                       np.ascontiguousarray(g.weight, np.int32))
+
+
 # ---- partitioned iteration (the distributed-CPU compute step) ----
 
 def pagerank_partitioned(g: Graph, nparts: int, iters: int) -> np.ndarray:

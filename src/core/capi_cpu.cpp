@@ -44,6 +44,9 @@ void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                   uint32_t* coreness);
 void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
              uint32_t* label);
+E_ID msf_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+             const WeightType* weight, V_ID* lo, V_ID* hi, WeightType* w,
+             uint8_t* in_forest, int64_t* total, uint32_t* label);
 void cf_init(V_ID nv, int K, float* vec);
 void cf_iter_part(V_ID row_left, V_ID row_right, E_ID col_left,
                   const E_ID* col_end, const V_ID* src, const WeightType* w,
@@ -267,6 +270,16 @@ void lux_coreness_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
 void lux_scc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                  const uint32_t* src, uint32_t* label) {
   scc_cpu(nv, ne, col_end, src, label);
+}
+// lo, hi u32[ne], w i32[ne], in_forest u8[ne]: the first m entries are
+// filled in, the simple edges in key order; total: the forest's weight;
+// label u32[nv]. Returns m.
+uint64_t lux_msf_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                     const uint32_t* src, const int32_t* weight, uint32_t* lo,
+                     uint32_t* hi, int32_t* w, uint8_t* in_forest,
+                     int64_t* total, uint32_t* label) {
+  return msf_cpu(nv, ne, col_end, src, weight, lo, hi, w, in_forest, total,
+                 label);
 }
 void lux_cf_init(uint32_t nv, int K, float* vec) { cf_init(nv, K, vec); }
 void lux_cf_iter_part(uint32_t row_left, uint32_t row_right,

@@ -616,6 +616,69 @@ void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   }
 }
 
+// ---------- minimum spanning forest ----------
+// Exact oracle of MSFEngine (no reference equivalent), on the simple
+// undirected graph of tc_cpu. The weight of {lo, hi} is the minimum weight
+// over all its occurrences in either direction: the (key, w) pairs are
+// sorted and the first of each key kept, which also lists the edges
+// ascending by key = (lo << 32) | hi, so the position is the edge id e.
+// Kruskal over the strict order (w, e) with a union-find whose roots are
+// the largest ids: label[v] = the largest vertex id of v's component.
+// lo / hi / w / in_forest: room for ne entries; returns m. No rounds, no
+// per-component search.
+E_ID msf_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+             const WeightType* weight, V_ID* lo, V_ID* hi, WeightType* w,
+             uint8_t* in_forest, int64_t* total, uint32_t* label) {
+  std::vector<std::pair<uint64_t, WeightType>> kw;
+  kw.reserve(ne);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v || s >= nv) continue;
+      V_ID l = std::min(s, v), h = std::max(s, v);
+      kw.emplace_back(((uint64_t)l << 32) | h, weight[i]);
+    }
+    b = col_end[v];
+  }
+  std::sort(kw.begin(), kw.end());
+  E_ID m = 0;
+  for (size_t i = 0; i < kw.size(); i++) {
+    if (i && kw[i].first == kw[i - 1].first) continue;
+    lo[m] = (V_ID)(kw[i].first >> 32);
+    hi[m] = (V_ID)(kw[i].first & 0xFFFFFFFFu);
+    w[m] = kw[i].second;
+    in_forest[m] = 0;
+    m++;
+  }
+  std::vector<E_ID> order(m);
+  for (E_ID e = 0; e < m; e++) order[e] = e;
+  std::sort(order.begin(), order.end(), [&](E_ID x, E_ID y) {
+    return w[x] != w[y] ? w[x] < w[y] : x < y;
+  });
+  std::vector<V_ID> parent(nv);
+  for (V_ID v = 0; v < nv; v++) parent[v] = v;
+  auto find = [&](V_ID v) {
+    while (parent[v] != v) {
+      parent[v] = parent[parent[v]];
+      v = parent[v];
+    }
+    return v;
+  };
+  int64_t sum = 0;
+  for (E_ID k = 0; k < m; k++) {
+    E_ID e = order[k];
+    V_ID ra = find(lo[e]), rb = find(hi[e]);
+    if (ra == rb) continue;
+    parent[std::min(ra, rb)] = std::max(ra, rb);
+    in_forest[e] = 1;
+    sum += w[e];
+  }
+  *total = sum;
+  for (V_ID v = 0; v < nv; v++) label[v] = find(v);
+  return m;
+}
+
 // ---------- Collaborative filtering ----------
 
 void cf_init(V_ID nv, int K, float* vec) {

@@ -467,4 +467,62 @@ void lux_gpu_scc_check_pairs(uint64_t stream, lux::V_ID nv, lux::E_ID ne,
                              const lux::V_ID* out_col, const uint32_t* label,
                              unsigned long long* bad);
 
+// msf.hip (minimum spanning forest by synchronous Boruvka rounds, single
+// rank). optr / oadj: the id-order DAG of the simple graph; arc e of it is
+// simple edge e = (elo[e], ehi[e]) with ehi = oadj, weight w[e] = the minimum
+// over the edge's occurrences. aptr u64[nv+1] / anbr, aeid u32[2m]: the
+// full symmetric adjacency, every entry with its edge id. hubrow: the rows
+// longer than hub; item i is chunk item_chunk[i] (hub entries) of row
+// hubrow[item_row[i]]. meta u64[meta_words]: [0] components with an edge,
+// [1] hooks and [2] entries walked of the last scan / hook; [3] the total
+// weight (i64 bits) and [4] the forest edges of the solve; [5] errors.
+struct lux_msf_args {
+  const lux::E_ID* aptr;       // u64[nv+1]
+  const lux::V_ID* anbr;       // u32[2m]
+  const uint32_t* aeid;        // u32[2m]
+  const lux::V_ID* elo;        // u32[m]
+  const lux::V_ID* ehi;        // u32[m]
+  const int* w;                // i32[m]
+  lux::V_ID* comp;             // u32[nv]
+  lux::V_ID* parent;           // u32[nv]
+  unsigned long long* best;    // u64[nv]
+  uint8_t* dead;               // u8[nv]
+  uint8_t* inforest;           // u8[m]
+  const lux::V_ID* hubrow;     // u32[nhub]
+  uint32_t* hubext;            // u32[nhub]
+  const uint32_t* item_row;    // u32[nitems]
+  const uint32_t* item_chunk;  // u32[nitems]
+  unsigned long long* meta;    // u64[meta_words]
+  lux::E_ID m;
+  lux::V_ID nv;
+  uint32_t nhub, nitems;
+  uint32_t hub;  // rows longer than this are walked in chunks of hub entries
+  int use_dead;  // 0: walk every row in every scan
+};
+uint32_t lux_gpu_msf_hub_default();
+uint32_t lux_gpu_msf_meta_words();
+void lux_gpu_msf_weights(uint64_t stream, lux::V_ID nv, lux::E_ID ne,
+                         const lux::E_ID* row_ptr, const lux::V_ID* col,
+                         const int* weight, const lux::E_ID* optr,
+                         const lux::V_ID* oadj, int* w,
+                         unsigned long long* err);
+void lux_gpu_msf_adj_fill(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                          const lux::E_ID* optr, const lux::V_ID* oadj,
+                          const lux::E_ID* aptr, uint32_t* cursor,
+                          lux::V_ID* anbr, uint32_t* aeid, lux::V_ID* elo);
+void lux_gpu_msf_init(uint64_t stream, const lux_msf_args* a);
+int lux_gpu_msf_scan(uint64_t stream, const lux_msf_args* a, uint32_t stamp);
+void lux_gpu_msf_hook(uint64_t stream, const lux_msf_args* a);
+void lux_gpu_msf_flatten(uint64_t stream, const lux_msf_args* a);
+void lux_gpu_msf_labels(uint64_t stream, lux::V_ID nv, const lux::V_ID* comp,
+                        lux::V_ID* maxid, lux::V_ID* labels);
+void lux_gpu_msf_check(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                       const lux::E_ID* aptr, const uint32_t* aeid,
+                       const lux::V_ID* elo, const lux::V_ID* ehi,
+                       const int* w, const uint8_t* mask,
+                       const lux::V_ID* labels, lux::V_ID* pf, lux::V_ID* pa,
+                       unsigned long long* out);
+int lux_gpu_msf_set_mark(uint64_t stream, uint8_t* mask, lux::E_ID m,
+                         lux::E_ID e, int value);
+
 }  // extern "C"
