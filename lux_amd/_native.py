@@ -354,6 +354,24 @@ def coreness_cpu(nv, ne, col_end, src):
     return core
 
 
+COLOURING_ORDERS = ("degree", "id", "hash")
+
+
+def greedy_colouring_cpu(nv, ne, col_end, src, order, seed):
+    """colour i32[nv] of the greedy colouring in priority order."""
+    if order not in COLOURING_ORDERS:
+        raise ValueError(f"order must be one of {COLOURING_ORDERS}, "
+                         f"got {order!r}")
+    colour = np.empty(nv, np.int32)
+    rc = cpu.lux_greedy_colouring_cpu(
+        ctypes.c_uint32(nv), ctypes.c_uint64(ne), ptr(col_end, u64p),
+        ptr(src, u32p), ctypes.c_int(COLOURING_ORDERS.index(order)),
+        ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ptr(colour, i32p))
+    if rc != 0:
+        raise ValueError(f"greedy_colouring_cpu: bad order {order!r}")
+    return colour
+
+
 def scc_cpu(nv, ne, col_end, src):
     """label u32[nv]: the largest vertex id of each vertex's SCC."""
     label = np.empty(nv, np.uint32)

@@ -830,3 +830,97 @@ def msf_set_mark(stream, mask, m, e, value):
                                     ctypes.c_int(value))
     if rc != 0:
         raise ValueError(f"msf_set_mark: edge {e} outside [0, {m})")
+
+
+# ---- greedy colouring / maximal independent set (colouring.hip) ----
+
+class GcolArgs(ctypes.Structure):
+    """lux_gcol_args: the predecessor / successor rows and the state of a
+    solve."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "pptr", "padj", "sptr", "sadj", "colour", "pending", "order", "hubq",
+        "rtail", "meta")] + \
+        [("nv", ctypes.c_uint32), ("hubcap", ctypes.c_uint32),
+         ("hub", ctypes.c_uint32)]
+
+
+# meta words
+GCOL_M_TAIL, GCOL_M_HUBTAIL, GCOL_M_FUSED, GCOL_M_HEAD = range(4)
+
+
+def _gcol_const(name):
+    f = getattr(lib(), name)
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def gcol_hub_default():
+    """GCOL_HUB: the longest row the row role takes when LUX_GCOL_HUB is
+    unset."""
+    return _gcol_const("lux_gpu_gcol_hub_default")
+
+
+def gcol_fuse_default():
+    """GCOL_FUSE: the tail kernel's round size when LUX_GCOL_FUSE is
+    unset."""
+    return _gcol_const("lux_gpu_gcol_fuse_default")
+
+
+def gcol_fuse_max():
+    return _gcol_const("lux_gpu_gcol_fuse_max")
+
+
+def gcol_window_bits():
+    """GCOL_WINDOW: the colours one pass of a select covers."""
+    return _gcol_const("lux_gpu_gcol_window_bits")
+
+
+def gcol_meta_words():
+    return _gcol_const("lux_gpu_gcol_meta_words")
+
+
+def gcol_args(pptr, padj, sptr, sadj, colour, pending, order, hubq, rtail,
+              meta, nv, hubcap, hub):
+    return GcolArgs(*(t.data_ptr() for t in (
+        pptr, padj, sptr, sadj, colour, pending, order, hubq, rtail, meta)),
+        nv, hubcap, hub)
+
+
+def gcol_split_count(stream, nv, m, optr, oadj, rank, npred, nsucc):
+    lib().lux_gpu_gcol_split_count(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                                   dp(oadj), dp(rank), dp(npred), dp(nsucc))
+
+
+def gcol_split_fill(stream, nv, m, optr, oadj, rank, pptr, sptr, pcur, scur,
+                    padj, sadj):
+    lib().lux_gpu_gcol_split_fill(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                                  dp(oadj), dp(rank), dp(pptr), dp(sptr),
+                                  dp(pcur), dp(scur), dp(padj), dp(sadj))
+
+
+def gcol_seed(stream, a):
+    lib().lux_gpu_gcol_seed(_u64(stream), ctypes.byref(a))
+
+
+def gcol_step(stream, a, head, tail, hubhead, hubtail):
+    """One round: order[head:tail) and the hubq items [hubhead, hubtail)."""
+    rc = lib().lux_gpu_gcol_step(_u64(stream), ctypes.byref(a), _u32(head),
+                                 _u32(tail), _u32(hubhead), _u32(hubtail))
+    if rc != 0:
+        raise ValueError(f"gcol_step: bad round [{head}, {tail}) / "
+                         f"[{hubhead}, {hubtail}), hub={a.hub}")
+
+
+def gcol_tail(stream, a, head, tail, hubtail, fuse, round0):
+    """Small rounds from order[head:tail) on, one workgroup."""
+    rc = lib().lux_gpu_gcol_tail(_u64(stream), ctypes.byref(a), _u32(head),
+                                 _u32(tail), _u32(hubtail), _u32(fuse),
+                                 _u32(round0))
+    if rc != 0:
+        raise ValueError(f"gcol_tail: round [{head}, {tail}) does not "
+                         f"qualify (fuse={fuse}, hub={a.hub})")
+
+
+def gcol_check(stream, nv, pptr, padj, sptr, sadj, colour, bad):
+    lib().lux_gpu_gcol_check(_u64(stream), _u32(nv), dp(pptr), dp(padj),
+                             dp(sptr), dp(sadj), dp(colour), dp(bad))

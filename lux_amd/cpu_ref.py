@@ -116,6 +116,20 @@ def coreness(g: Graph) -> np.ndarray:
     return nat.coreness_cpu(g.nv, g.ne, g.col_end, g.src)
 
 
+def greedy_colouring(g: Graph, order="degree", seed=1) -> np.ndarray:
+    """colour i32[nv] on the simple undirected graph of triangles(): the
+    sequential greedy colouring in the priority order `order` — degree:
+    larger simple degree first, ties by smaller id; id: smaller id first;
+    hash: smaller splitmix64(seed ^ v) >> 1 first, ties by smaller id.
+    colour[v] is the smallest colour that no neighbour preceding v has, so
+    colour == 0 is the lexicographically first maximal independent set. C++,
+    one sequential pass over its own adjacency and its own priority
+    permutation with a stamp array; shares no code with tc_engine.orient
+    and no schedule with ColouringEngine's rounds."""
+    return nat.greedy_colouring_cpu(g.nv, g.ne, g.col_end, g.src, order,
+                                    seed)
+
+
 def scc(g: Graph) -> np.ndarray:
     """label u32[nv] of the directed graph as loaded (row v of the CSC lists
     the sources u of the edges u -> v; parallel edges and self-loops change

@@ -42,6 +42,9 @@ E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                V_ID* edges, uint32_t* support, uint32_t* trussness);
 void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                   uint32_t* coreness);
+int greedy_colouring_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
+                         const V_ID* src, int order, uint64_t seed,
+                         int32_t* colour);
 void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
              uint32_t* label);
 E_ID msf_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
@@ -266,6 +269,13 @@ uint64_t lux_truss_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
 void lux_coreness_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                       const uint32_t* src, uint32_t* coreness) {
   coreness_cpu(nv, ne, col_end, src, coreness);
+}
+// order 0 degree / 1 id / 2 hash (seed); colour i32[nv]. Returns -1 on an
+// unknown order.
+int lux_greedy_colouring_cpu(uint32_t nv, uint64_t ne,
+                             const uint64_t* col_end, const uint32_t* src,
+                             int order, uint64_t seed, int32_t* colour) {
+  return greedy_colouring_cpu(nv, ne, col_end, src, order, seed, colour);
 }
 void lux_scc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                  const uint32_t* src, uint32_t* label) {

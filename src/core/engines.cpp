@@ -555,6 +555,76 @@ void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   }
 }
 
+// ---------- greedy colouring ----------
+// Exact oracle of ColouringEngine (no reference equivalent), on the same
+// simple undirected graph as tc_cpu. A strict total order "v precedes u":
+// order 0 (degree) deg[v] > deg[u], or equal and v < u; order 1 (id) v < u;
+// order 2 (hash) h(v) < h(u), or equal and v < u, h(v) =
+// splitmix64(seed ^ v) >> 1. colour[v] = the smallest colour no preceding
+// neighbour has. One sequential pass in priority order: when v's turn comes
+// its coloured neighbours are exactly its predecessors; stamp[c] == v + 1
+// marks the colours they hold. No rounds, no queue. Returns -1 on an unknown
+// order.
+int greedy_colouring_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
+                         const V_ID* src, int order, uint64_t seed,
+                         int32_t* colour) {
+  if (order < 0 || order > 2) return -1;
+  std::vector<uint64_t> keys;
+  keys.reserve(ne);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v) continue;
+      V_ID lo = std::min(s, v), hi = std::max(s, v);
+      keys.push_back(((uint64_t)lo << 32) | hi);
+    }
+    b = col_end[v];
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  const E_ID m = keys.size();
+  std::vector<E_ID> ptr((size_t)nv + 1, 0);
+  for (E_ID e = 0; e < m; e++) {
+    ptr[(keys[e] >> 32) + 1]++;
+    ptr[(keys[e] & 0xFFFFFFFFu) + 1]++;
+  }
+  for (V_ID v = 0; v < nv; v++) ptr[v + 1] += ptr[v];
+  std::vector<V_ID> nbr(2 * m);
+  {
+    std::vector<E_ID> fill(ptr.begin(), ptr.end() - 1);
+    for (E_ID e = 0; e < m; e++) {
+      V_ID lo = (V_ID)(keys[e] >> 32), hi = (V_ID)(keys[e] & 0xFFFFFFFFu);
+      nbr[fill[lo]++] = hi;
+      nbr[fill[hi]++] = lo;
+    }
+  }
+  // the priority permutation: ascending (key, id)
+  std::vector<uint64_t> key(nv, 0);
+  for (V_ID v = 0; v < nv; v++) {
+    if (order == 0) key[v] = ~(uint64_t)(ptr[v + 1] - ptr[v]);
+    if (order == 2) key[v] = splitmix64(seed ^ (uint64_t)v) >> 1;
+  }
+  std::vector<V_ID> perm(nv);
+  for (V_ID v = 0; v < nv; v++) perm[v] = v;
+  std::sort(perm.begin(), perm.end(), [&](V_ID x, V_ID y) {
+    return key[x] != key[y] ? key[x] < key[y] : x < y;
+  });
+  std::vector<V_ID> stamp((size_t)nv + 1, 0);
+  for (V_ID v = 0; v < nv; v++) colour[v] = -1;
+  for (V_ID k = 0; k < nv; k++) {
+    V_ID v = perm[k];
+    for (E_ID i = ptr[v]; i < ptr[v + 1]; i++) {
+      int32_t c = colour[nbr[i]];
+      if (c >= 0) stamp[c] = v + 1;
+    }
+    int32_t c = 0;
+    while (stamp[c] == v + 1) c++;
+    colour[v] = c;
+  }
+  return 0;
+}
+
 // ---------- strongly connected components ----------
 // Exact oracle of SCCEngine (no reference equivalent), on the directed graph
 // as loaded: row v of the CSC lists the sources u of the edges u -> v.

@@ -525,4 +525,55 @@ void lux_gpu_msf_check(uint64_t stream, lux::V_ID nv, lux::E_ID m,
 int lux_gpu_msf_set_mark(uint64_t stream, uint8_t* mask, lux::E_ID m,
                          lux::E_ID e, int value);
 
+// colouring.hip (greedy colouring in a fixed priority order and the first
+// maximal independent set, Jones-Plassmann rounds; single rank). optr / oadj:
+// the id-order DAG of the simple graph; rank u32[nv]: a smaller rank
+// precedes. pptr / padj: the predecessor rows, sptr / sadj: the successor
+// rows, m entries each. lux_gcol_args is the split graph and the state of a
+// solve. hubq items are {vertex, item}: item 0xFFFFFFFF selects the colour
+// of a vertex whose predecessor row is longer than hub, item c notifies
+// entries [c * hub, (c + 1) * hub) of a successor row longer than hub.
+// meta u32[meta_words]: [0] the order cursor, [1] the hubq cursor, [2]
+// rounds done and [3] first unprocessed entry of the last tail launch.
+struct lux_gcol_args {
+  const lux::E_ID* pptr;  // u64[nv+1]
+  const lux::V_ID* padj;  // u32[m]
+  const lux::E_ID* sptr;  // u64[nv+1]
+  const lux::V_ID* sadj;  // u32[m]
+  int* colour;            // i32[nv], -1 until coloured
+  int* pending;           // i32[nv], the uncoloured predecessors
+  lux::V_ID* order;       // u32[nv], append-only
+  uint32_t* hubq;         // u32[2 * hubcap]
+  uint32_t* rtail;        // u32[nv]: the order cursor after each fused round
+  uint32_t* meta;         // u32[meta_words]
+  lux::V_ID nv;
+  uint32_t hubcap;  // items
+  uint32_t hub;     // rows longer than this go through hubq
+};
+uint32_t lux_gpu_gcol_hub_default();
+uint32_t lux_gpu_gcol_fuse_default();
+uint32_t lux_gpu_gcol_fuse_max();
+uint32_t lux_gpu_gcol_window_bits();
+uint32_t lux_gpu_gcol_meta_words();
+void lux_gpu_gcol_split_count(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                              const lux::E_ID* optr, const lux::V_ID* oadj,
+                              const uint32_t* rank, uint32_t* npred,
+                              uint32_t* nsucc);
+void lux_gpu_gcol_split_fill(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                             const lux::E_ID* optr, const lux::V_ID* oadj,
+                             const uint32_t* rank, const lux::E_ID* pptr,
+                             const lux::E_ID* sptr, uint32_t* pcur,
+                             uint32_t* scur, lux::V_ID* padj,
+                             lux::V_ID* sadj);
+void lux_gpu_gcol_seed(uint64_t stream, const lux_gcol_args* g);
+int lux_gpu_gcol_step(uint64_t stream, const lux_gcol_args* g, uint32_t head,
+                      uint32_t tail, uint32_t hubhead, uint32_t hubtail);
+int lux_gpu_gcol_tail(uint64_t stream, const lux_gcol_args* g, uint32_t head,
+                      uint32_t tail, uint32_t hubtail, uint32_t fuse,
+                      uint32_t round0);
+void lux_gpu_gcol_check(uint64_t stream, lux::V_ID nv, const lux::E_ID* pptr,
+                        const lux::V_ID* padj, const lux::E_ID* sptr,
+                        const lux::V_ID* sadj, const int* colour,
+                        unsigned long long* bad);
+
 }  // extern "C"
