@@ -367,6 +367,26 @@ def pull_slots_stream_hot_iter(stream, n0, cidx0, nt, tile0, off0, scol0, n1,
         raise ValueError(f"pull_slots_stream_hot_iter: unsupported k={k}")
 
 
+def pull_slots_stream_hot_wide_iter(stream, n0, cidx0, nt, tile0, off0,
+                                    scol0, n1, cidx1, rng1, n2, cidx2, rng2,
+                                    col, gold, acc, lo, hi, ks, kw,
+                                    max_groups=0):
+    """scol0 / col are the tensors themselves: their lengths set the role
+    split. max_groups: 0 = eight workgroups per CU."""
+    rc = lib().lux_gpu_pull_slots_stream_hot_wide_iter(
+        _u64(stream), _u32(n0), dp(cidx0), _u32(nt), dp(tile0), dp(off0),
+        dp(scol0), _u64(0 if scol0 is None else scol0.numel()), _u32(n1),
+        dp(cidx1), dp(rng1), _u32(n2), dp(cidx2), dp(rng2), dp(col),
+        _u64(col.numel()), dp(gold), dp(acc), _u32(lo), _u32(hi),
+        ctypes.c_int(ks), ctypes.c_int(kw), _u32(max_groups))
+    if rc == -1:
+        raise ValueError("pull_slots_stream_hot_wide_iter: unsupported "
+                         f"(ks, kw)=({ks}, {kw})")
+    if rc != 0:
+        raise RuntimeError("pull_slots_stream_hot_wide_iter: the runtime "
+                           "refused the CU count or the LDS size")
+
+
 def pull_fill_inactive_pr(stream, vp, row_ptr, out, deg, row_left,
                           init_rank):
     lib().lux_gpu_pull_fill_inactive_pr(_u64(stream), _u32(vp), dp(row_ptr),

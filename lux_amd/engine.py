@@ -30,6 +30,8 @@ LLC_BLOCK_SHIFT = 23  # 2^23 verts * 4 B = 32 MB gather window: measured
 PULL_STREAM_DEFAULT = "1"  # LUX_PULL_STREAM when unset (BENCHLOG r4.1)
 PULL_HOT_DEFAULT = "1"  # LUX_PULL_HOT when unset (BENCHLOG r9.1)
 PULL_HOT_LDS_DEFAULT = "2048"  # LUX_PULL_HOT_LDS when unset (BENCHLOG r9.1)
+PULL_HOT_WIDE_DEFAULT = "1"  # LUX_PULL_HOT_WIDE when unset (BENCHLOG r16.1)
+PULL_HOT_WIDE_PREFIX = (8192, 16384)  # (ks, kw) of the wide sweep
 HOT_BLOCK_SHIFT = 24  # window width of the hot-ordered PageRank sweeps: the
 # gathered part of a window is its first ~40 %, so 64 MB windows hold what
 # 32 MB ones did and halve the acc passes (RMAT-27: 15.04 vs 15.36 ms/iter;
@@ -134,8 +136,18 @@ def pull_hot_lds():
     return k
 
 
+def pull_hot_wide_enabled():
+    """LUX_PULL_HOT_WIDE: the hot-order stream sweeps with an LDS prefix run
+    as 1024-thread workgroups, two resident per CU, holding
+    PULL_HOT_WIDE_PREFIX sources (stream role, wave and chunk roles) instead
+    of LUX_PULL_HOT_LDS in 256-thread ones. Same row sums bit for bit; =0 /
+    =1 for A/B runs."""
+    import os
+    return os.environ.get("LUX_PULL_HOT_WIDE", PULL_HOT_WIDE_DEFAULT) != "0"
+
+
 def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
-                          hot_lds=0):
+                          hot_lds=0, hot_wide=None, max_groups=0):
     """PR_SUM fold-sweeps on the slot path (GraphPart.prepare_pull_slots):
     one launch per src window, accumulating into the active-row array
     acc[na] — acc[i] belongs to local row part.active[i]. Same window
@@ -145,13 +157,25 @@ def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
     (GraphPart.prepare_pull_hot, built by the caller); oldv is then the
     gather table in that order, oldv[part.pos[v]] = value of vertex v.
     hot_lds (hot + stream only): that many of each window's hottest
-    sources are gathered from LDS (pull_hot_lds)."""
+    sources are gathered from LDS (pull_hot_lds). hot_wide (with hot_lds
+    != 0): a (ks, kw) prefix pair, the sweeps then run as the wide kernel
+    with max_groups workgroups (0: eight per CU)."""
     s = _stream()
     if stream is None:
         stream = pull_stream_enabled()
     col, scol0 = ("hcol", "hscol0") if hot else ("col", "scol0")
     if stream:
         part.prepare_pull_stream(hot=hot)  # no-op once built
+        if hot and hot_lds and hot_wide:
+            ks, kw = hot_wide
+            for src in part.slot_srcs:
+                ng.pull_slots_stream_hot_wide_iter(
+                    s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
+                    src["off0"], src["hscol0"], src["n1"], src["cidx1"],
+                    src["rng1"], src["n2"], src["cidx2"], src["rng2"],
+                    src["hcol"], oldv, acc, src["lo"], src["hi"], ks, kw,
+                    max_groups)
+            return
         if hot and hot_lds:
             for src in part.slot_srcs:
                 ng.pull_slots_stream_hot_iter(
@@ -964,6 +988,10 @@ class PagerankEngine:
         # role on hot-ordered tables only)
         self._hot_lds = pull_hot_lds() \
             if self._hot and self._stream_role else 0
+        # LUX_PULL_HOT_WIDE: those sweeps by 1024-thread workgroups with a
+        # longer prefix (None: the 256-thread kernel and _hot_lds sources)
+        self._hot_wide = PULL_HOT_WIDE_PREFIX \
+            if self._hot_lds and pull_hot_wide_enabled() else None
         if self._slots:
             self.acc = torch.empty(max(part.na, 1), dtype=F32,
                                    device=device)
@@ -997,7 +1025,8 @@ class PagerankEngine:
             self.acc.zero_()
             run_pull_slots_sweeps(p, self.gold if self._hot else self.old,
                                   self.acc, stream=self._stream_role,
-                                  hot=self._hot, hot_lds=self._hot_lds)
+                                  hot=self._hot, hot_lds=self._hot_lds,
+                                  hot_wide=self._hot_wide)
             # the kernel boundary after the last sweep makes the in-place
             # write safe: nothing reads `old` (or gold) until the next
             # step's sweeps

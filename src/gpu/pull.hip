@@ -22,7 +22,9 @@
 // one wave per tile of consecutive slots, lane = edge, row sums out of LDS.
 // In hot order (sources ranked by out-degree inside each src window) the
 // same sweeps run on permuted column copies and a permuted rank table, and
-// lux_gpu_pull_slots_stream_hot_iter keeps a window's hottest sources in LDS.
+// lux_gpu_pull_slots_stream_hot_iter keeps a window's hottest sources in LDS
+// (lux_gpu_pull_slots_stream_hot_wide_iter: four to eight times as many, in
+// 1024-thread workgroups).
 #include "gpu_common.h"
 
 namespace lux {
@@ -205,6 +207,17 @@ __device__ __forceinline__ float hot_load(const float* oldv,
   const float* p = r < (V_ID)K ? hot + r : oldv + c;
   return *p;
 }
+// The wide sweep (pull_slots_stream_hot_wide_kernel) keeps its prefix in the
+// workgroup's dynamic LDS: K sources from float offset OFF on, both fixed by
+// the workgroup's role.
+template <int K, int OFF>
+struct PullArgsWide : PullArgs {
+  V_ID lo;
+};
+__device__ __forceinline__ float* wide_lds() {
+  extern __shared__ float wide_lds_[];
+  return wide_lds_;
+}
 
 // Result store for the non-atomic bins. The iteration contract: newv is
 // pre-seeded (PR: zeros; labels: the old label slice) before the sweep(s),
@@ -281,14 +294,11 @@ __device__ __forceinline__ typename Val<M>::T gather_edges(
 }
 // gather_range<PR_SUM> with the hot prefix served from LDS: same four-way
 // pipeline, same association order, same values
-template <PullMode M, int K>
-__device__ __forceinline__ float gather_edges(const PullArgsHot<K>& a,
-                                              const float* oldv, E_ID j,
-                                              E_ID e, E_ID step) {
-  static_assert(M == PR_SUM, "hot prefix: float sums only");
-  const float* hot = hot_prefix<K>();
-  const V_ID* col = a.col;
-  V_ID lo = a.lo;
+template <int K>
+__device__ __forceinline__ float gather_range_hot(const float* oldv,
+                                                  const float* hot, V_ID lo,
+                                                  const V_ID* col, E_ID j,
+                                                  E_ID e, E_ID step) {
   float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
   for (; j + 3 * step < e; j += 4 * step) {
     V_ID c0 = col[j], c1 = col[j + step], c2 = col[j + 2 * step],
@@ -301,6 +311,20 @@ __device__ __forceinline__ float gather_edges(const PullArgsHot<K>& a,
   for (; j < e; j += step) a0 = a0 + hot_load<K>(oldv, hot, lo, col[j]);
   return (a0 + a1) + (a2 + a3);
 }
+template <PullMode M, int K>
+__device__ __forceinline__ float gather_edges(const PullArgsHot<K>& a,
+                                              const float* oldv, E_ID j,
+                                              E_ID e, E_ID step) {
+  static_assert(M == PR_SUM, "hot prefix: float sums only");
+  return gather_range_hot<K>(oldv, hot_prefix<K>(), a.lo, a.col, j, e, step);
+}
+template <PullMode M, int K, int OFF>
+__device__ __forceinline__ float gather_edges(const PullArgsWide<K, OFF>& a,
+                                              const float* oldv, E_ID j,
+                                              E_ID e, E_ID step) {
+  static_assert(M == PR_SUM, "hot prefix: float sums only");
+  return gather_range_hot<K>(oldv, wide_lds() + OFF, a.lo, a.col, j, e, step);
+}
 
 // one gathered value, for the roles that do not go through gather_edges
 __device__ __forceinline__ float old_load(const PullArgs&, const float* oldv,
@@ -311,6 +335,11 @@ template <int K>
 __device__ __forceinline__ float old_load(const PullArgsHot<K>& a,
                                           const float* oldv, V_ID c) {
   return hot_load<K>(oldv, hot_prefix<K>(), a.lo, c);
+}
+template <int K, int OFF>
+__device__ __forceinline__ float old_load(const PullArgsWide<K, OFF>& a,
+                                          const float* oldv, V_ID c) {
+  return hot_load<K>(oldv, wide_lds() + OFF, a.lo, c);
 }
 
 // ---- where a bin entry's output row and edge range come from ----
@@ -555,14 +584,14 @@ __device__ __forceinline__ float lds_range_sum(const float* v, uint32_t j,
 
 // Wave-local throughout (no __syncthreads()): a wave's LDS accesses issue
 // in order, the wavefront fence only keeps the compiler from moving them.
-template <PullMode M, typename Args>
-__device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
-                                                 const SlotStream& st,
-                                                 const V_ID* cidx0,
-                                                 const Args& a) {
+// NW waves per workgroup; vals: the workgroup's NW tile buffers.
+template <PullMode M, uint32_t NW, typename Args>
+__device__ __forceinline__ void pull_stream_tiles(uint32_t blk, uint32_t nblk,
+                                                  const SlotStream& st,
+                                                  const V_ID* cidx0,
+                                                  const Args& a,
+                                                  float (*vals)[TILE_EDGES]) {
   static_assert(M == PR_SUM, "stream role: float sums only");
-  constexpr uint32_t NW = BLOCK / WAVE;
-  __shared__ float vals[NW][TILE_EDGES];
   const float* oldv = (const float*)a.oldv;
   float* acc = (float*)a.newv;
   uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -628,6 +657,16 @@ __device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
   }
 }
 
+template <PullMode M, typename Args>
+__device__ __forceinline__ void pull_stream_role(uint32_t blk, uint32_t nblk,
+                                                 const SlotStream& st,
+                                                 const V_ID* cidx0,
+                                                 const Args& a) {
+  constexpr uint32_t NW = BLOCK / WAVE;
+  __shared__ float vals[NW][TILE_EDGES];
+  pull_stream_tiles<M, NW>(blk, nblk, st, cidx0, a, vals);
+}
+
 template <PullMode M>
 __global__ void __launch_bounds__(BLOCK)
     pull_slots_stream_kernel(SlotBins s, SlotStream st, PullArgs a) {
@@ -663,6 +702,101 @@ __global__ void __launch_bounds__(BLOCK)
   } else {
     pull_stream_role<M>(blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, st,
                         s.cidx0, a);
+  }
+}
+
+// ---- wide hot sweep: 1024-thread workgroups, two resident per CU ----
+// Same three roles and the same row sums as pull_slots_stream_hot_kernel, but
+// a workgroup is 16 waves, so one prefix copy serves four times the waves and
+// can be four to eight times as long at the same 8 waves per SIMD. The grid
+// is a few workgroups per CU (every workgroup copies its prefix once per
+// launch) and the role loops grid-stride. One dynamic LDS allocation, laid out by role:
+//   stream role:      16 tile buffers (32 KB) | prefix of KS sources
+//   wave, chunk role: prefix of KW sources | 16 floats of reduction scratch
+constexpr int WIDE_BLOCK = 1024;
+constexpr uint32_t WIDE_NW = WIDE_BLOCK / WAVE;
+constexpr uint32_t WIDE_Q = WIDE_BLOCK / BLOCK;  // 256-thread quarters
+constexpr uint32_t WIDE_TILE_FLOATS = WIDE_NW * TILE_EDGES;
+constexpr uint32_t WIDE_SCRATCH = WIDE_Q * (BLOCK / WAVE);
+// Default grid per CU. Two workgroups are resident; with exactly those the
+// fixed role split decides the launch's tail (13.75 ms per RMAT-27 iteration
+// against 13.54 for the 256-thread kernel). Queued workgroups let dispatch
+// even the roles out and cost one more prefix copy each: 4 per CU 13.42 ms,
+// 8 per CU 13.12 ms (BENCHLOG r16.1).
+constexpr uint32_t WIDE_GROUPS_PER_CU = 8;
+
+template <int KS, int KW>
+constexpr uint32_t wide_lds_bytes() {
+  uint32_t s = WIDE_TILE_FLOATS + KS, w = KW + WIDE_SCRATCH;
+  return 4 * (s > w ? s : w);
+}
+
+// pull_chunk_role for a 1024-thread workgroup: every 256-thread quarter takes
+// its own chunk entry, strides it by 256 and folds its four waves in its own
+// scratch, so a chunk's partial is the float pull_chunk_role gives. The trip
+// count is the workgroup's: a quarter without an entry idles through the
+// barriers.
+template <int K, int OFF>
+__device__ __forceinline__ void pull_chunk_role_wide(
+    uint32_t blk, uint32_t nblk, uint32_t n2, const SlotRows& src,
+    const PullArgsWide<K, OFF>& a, float* scratch) {
+  using V = Val<PR_SUM>;
+  const float* oldv = (const float*)a.oldv;
+  float* newv = (float*)a.newv;
+  uint32_t q = threadIdx.x / BLOCK, tq = threadIdx.x % BLOCK;
+  uint32_t lane = tq & (WAVE - 1), wid = tq >> 6;
+  float* lds = scratch + q * (BLOCK / WAVE);
+  for (uint64_t base = (uint64_t)blk * WIDE_Q; base < n2;
+       base += (uint64_t)nblk * WIDE_Q) {
+    uint64_t i = base + q;
+    bool work = i < n2;  // uniform in the quarter
+    V_ID v = 0;
+    if (work) {
+      uint32_t chunk = 0;
+      v = src.row(i, chunk);
+      E_ID b, e;
+      src.range(i, v, chunk, b, e);
+      float acc = gather_edges<PR_SUM>(a, oldv, b + tq, e, BLOCK);
+      acc = V::reduce_wave(acc);
+      if (lane == 0) lds[wid] = acc;
+    }
+    __syncthreads();
+    if (work && tq == 0) {
+      float acc = lds[0];
+      for (int w = 1; w < BLOCK / WAVE; w++) acc = V::comb(acc, lds[w]);
+      V::atom(&newv[v], acc);
+    }
+    __syncthreads();
+  }
+}
+
+template <int KS, int KW>
+__global__ void __launch_bounds__(WIDE_BLOCK, 8)
+    pull_slots_stream_hot_wide_kernel(SlotBins s, SlotStream st, PullArgs p,
+                                      V_ID lo, V_ID hi) {
+  uint32_t blk = blockIdx.x;
+  bool stream = blk >= s.g2 + s.g1;
+  float* hot = wide_lds() + (stream ? WIDE_TILE_FLOATS : 0);
+  uint32_t k = stream ? KS : KW;
+  const float* oldv = (const float*)p.oldv;
+  for (uint32_t i = threadIdx.x; i < k; i += WIDE_BLOCK) {
+    uint64_t pos = (uint64_t)lo + i;
+    hot[i] = pos < hi ? oldv[pos] : 0.0f;
+  }
+  __syncthreads();
+  if (blk < s.g2) {
+    PullArgsWide<KW, 0> a{p, lo};
+    pull_chunk_role_wide(blk, s.g2, s.n2, SlotRows{s.cidx2, s.rng2}, a,
+                         wide_lds() + KW);
+  } else if (!stream) {
+    PullArgsWide<KW, 0> a{p, lo};
+    pull_wave_role<PR_SUM>(blk - s.g2, s.g1, s.n1, SlotRows{s.cidx1, s.rng1},
+                           a);
+  } else {
+    PullArgsWide<KS, WIDE_TILE_FLOATS> a{p, lo};
+    pull_stream_tiles<PR_SUM, WIDE_NW>(
+        blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, st, s.cidx0, a,
+        (float(*)[TILE_EDGES])wide_lds());
   }
 }
 
@@ -1183,6 +1317,95 @@ int lux_gpu_pull_slots_stream_hot_iter(
     default: LUX_HOT(4096); break;
   }
 #undef LUX_HOT
+  LUX_POST_LAUNCH(stream);
+  return 0;
+}
+
+// Workgroups per role for a grid of g: in proportion to the roles' edge
+// counts, at least one for a role with work, none for a role without, and no
+// more than the role has trips for (per[r] entries per workgroup and trip).
+static void wide_split(uint32_t g, const uint64_t edges[3],
+                       const uint64_t work[3], const uint32_t per[3],
+                       uint32_t out[3]) {
+  uint64_t tot = 0;
+  uint32_t roles = 0, sum = 0;
+  for (int r = 0; r < 3; r++)
+    if (work[r]) tot += edges[r] ? edges[r] : 1, roles++;
+  if (g < roles) g = roles;
+  for (int r = 0; r < 3; r++) {
+    uint64_t e = edges[r] ? edges[r] : 1;
+    out[r] = work[r] ? (uint32_t)((double)g * (double)e / (double)tot) : 0;
+    if (work[r] && !out[r]) out[r] = 1;
+    sum += out[r];
+  }
+  while (sum != g) {  // rounding: give to / take from the largest share
+    int big = 0;
+    for (int r = 1; r < 3; r++)
+      if (out[r] > out[big]) big = r;
+    if (sum < g) out[big]++, sum++;
+    else out[big]--, sum--;
+  }
+  for (int r = 0; r < 3; r++) {
+    uint64_t cap = (work[r] + per[r] - 1) / per[r];
+    if (out[r] > cap) out[r] = (uint32_t)cap;
+  }
+}
+
+// lux_gpu_pull_slots_stream_hot_iter by 1024-thread workgroups with a prefix
+// of ks sources in the stream role and kw in the wave and chunk roles
+// (pull_slots_stream_hot_wide_kernel). ne0 / ne: entries of scol0 / col, for
+// the role split. max_groups: 0 = WIDE_GROUPS_PER_CU workgroups per CU;
+// else the grid (at least one workgroup per role with work). Returns 0, -1
+// for a (ks, kw) that is not instantiated, or -2 if the runtime refuses the
+// CU count or the LDS size (nothing is launched either way).
+int lux_gpu_pull_slots_stream_hot_wide_iter(
+    uint64_t stream, uint32_t n0, const V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const V_ID* scol0,
+    uint64_t ne0, uint32_t n1, const V_ID* cidx1, const uint2* rng1,
+    uint32_t n2, const V_ID* cidx2, const uint2* rng2, const V_ID* col,
+    uint64_t ne, const float* gold, float* acc, V_ID lo, V_ID hi, int ks,
+    int kw, uint32_t max_groups) {
+  // (4096, 8192) and (8192, 8192) were measured and are not built: 0.7 and
+  // 0.6 ms per RMAT-27 iteration behind this pair (BENCHLOG r16.1)
+  if (ks != 8192 || kw != 16384) return -1;
+  uint32_t g = max_groups;
+  if (!g) {
+    static const uint32_t dflt = [] {
+      int dev = 0, cus = 0;
+      if (hipGetDevice(&dev) != hipSuccess ||
+          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                dev) != hipSuccess)
+        return 0u;
+      return (uint32_t)(WIDE_GROUPS_PER_CU * cus);
+    }();
+    if (!dflt) return -2;
+    g = dflt;
+  }
+  uint64_t work[3] = {n2, n1, n0 && nt ? nt : 0};
+  uint64_t e2 = (uint64_t)n2 * CHUNK_EDGES, rest = ne > ne0 ? ne - ne0 : 0;
+  if (e2 > rest) e2 = rest;
+  uint64_t edges[3] = {e2, rest - e2, ne0};
+  uint32_t per[3] = {WIDE_Q, WIDE_NW, WIDE_NW}, gr[3];
+  if (!(work[0] | work[1] | work[2])) return 0;
+  wide_split(g, edges, work, per, gr);
+  uint32_t g2 = gr[0], g1 = gr[1], g0 = gr[2];
+  SlotBins sb{n0, n1, n2, g1, g2, cidx0, cidx1, cidx2, nullptr, rng1, rng2};
+  SlotStream st{g0 ? nt : 0, tile0, off0, scol0};
+  PullArgs a{nullptr, col, gold, acc, nullptr, 0, 0.0f};
+#define LUX_WIDE(KS_, KW_)                                                    \
+  do {                                                                        \
+    auto kern = pull_slots_stream_hot_wide_kernel<KS_, KW_>;                  \
+    constexpr uint32_t bytes = wide_lds_bytes<KS_, KW_>();                    \
+    static_assert(2 * bytes <= 160 * 1024, "two workgroups per CU");          \
+    static const hipError_t raised = hipFuncSetAttribute(                     \
+        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,        \
+        (int)bytes);                                                          \
+    if (raised != hipSuccess) return -2;                                      \
+    hipLaunchKernelGGL(kern, dim3(g0 + g1 + g2), dim3(WIDE_BLOCK), bytes,     \
+                       (hipStream_t)stream, sb, st, a, lo, hi);               \
+  } while (0)
+  LUX_WIDE(8192, 16384);
+#undef LUX_WIDE
   LUX_POST_LAUNCH(stream);
   return 0;
 }

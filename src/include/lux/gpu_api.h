@@ -180,6 +180,17 @@ int lux_gpu_pull_slots_stream_hot_iter(
     uint32_t n1, const lux::V_ID* cidx1, const lux_uint2* rng1, uint32_t n2,
     const lux::V_ID* cidx2, const lux_uint2* rng2, const lux::V_ID* col,
     const float* gold, float* acc, lux::V_ID lo, lux::V_ID hi, int k);
+// the same sweep by 1024-thread workgroups, two resident per CU: ks sources
+// in LDS for the stream role, kw for the wave and chunk roles ((8192, 16384),
+// else -1 and no launch; -2: the runtime refused the LDS size). ne0 / ne: entries of scol0 / col, the role split follows the roles'
+// edge counts. max_groups: 0 = eight workgroups per CU, else the grid size.
+int lux_gpu_pull_slots_stream_hot_wide_iter(
+    uint64_t stream, uint32_t n0, const lux::V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const lux::V_ID* scol0,
+    uint64_t ne0, uint32_t n1, const lux::V_ID* cidx1, const lux_uint2* rng1,
+    uint32_t n2, const lux::V_ID* cidx2, const lux_uint2* rng2,
+    const lux::V_ID* col, uint64_t ne, const float* gold, float* acc,
+    lux::V_ID lo, lux::V_ID hi, int ks, int kw, uint32_t max_groups);
 void lux_gpu_pull_fill_inactive_pr(uint64_t stream, lux::V_ID vp,
                                    const lux::E_ID* row_ptr, float* out,
                                    const lux::V_ID* deg, lux::V_ID row_left,
