@@ -32,6 +32,7 @@ PULL_HOT_DEFAULT = "1"  # LUX_PULL_HOT when unset (BENCHLOG r9.1)
 PULL_HOT_LDS_DEFAULT = "2048"  # LUX_PULL_HOT_LDS when unset (BENCHLOG r9.1)
 PULL_HOT_WIDE_DEFAULT = "1"  # LUX_PULL_HOT_WIDE when unset (BENCHLOG r16.1)
 PULL_HOT_WIDE_PREFIX = (8192, 16384)  # (ks, kw) of the wide sweep
+PULL_HOT_QUEUE_DEFAULT = "1"  # LUX_PULL_HOT_QUEUE when unset (BENCHLOG r17.1)
 HOT_BLOCK_SHIFT = 24  # window width of the hot-ordered PageRank sweeps: the
 # gathered part of a window is its first ~40 %, so 64 MB windows hold what
 # 32 MB ones did and halve the acc passes (RMAT-27: 15.04 vs 15.36 ms/iter;
@@ -146,8 +147,18 @@ def pull_hot_wide_enabled():
     return os.environ.get("LUX_PULL_HOT_WIDE", PULL_HOT_WIDE_DEFAULT) != "0"
 
 
+def pull_hot_queue_enabled():
+    """LUX_PULL_HOT_QUEUE: the wide sweeps run on the resident set of
+    workgroups, which take small work items of the three roles from a
+    per-window queue, instead of eight workgroups per CU with a fixed role
+    each. Same row sums bit for bit; =0 / =1 for A/B runs."""
+    import os
+    return os.environ.get("LUX_PULL_HOT_QUEUE", PULL_HOT_QUEUE_DEFAULT) != "0"
+
+
 def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
-                          hot_lds=0, hot_wide=None, max_groups=0):
+                          hot_lds=0, hot_wide=None, max_groups=0,
+                          counters=None):
     """PR_SUM fold-sweeps on the slot path (GraphPart.prepare_pull_slots):
     one launch per src window, accumulating into the active-row array
     acc[na] — acc[i] belongs to local row part.active[i]. Same window
@@ -159,7 +170,9 @@ def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
     hot_lds (hot + stream only): that many of each window's hottest
     sources are gathered from LDS (pull_hot_lds). hot_wide (with hot_lds
     != 0): a (ks, kw) prefix pair, the sweeps then run as the wide kernel
-    with max_groups workgroups (0: eight per CU)."""
+    with max_groups workgroups (0: eight per CU). counters (with hot_wide):
+    i32[windows], all zero; the wide sweeps then take their work from a queue
+    (window w counts in counters[w]; max_groups 0: two workgroups per CU)."""
     s = _stream()
     if stream is None:
         stream = pull_stream_enabled()
@@ -168,6 +181,15 @@ def run_pull_slots_sweeps(part, oldv, acc, stream=None, hot=False,
         part.prepare_pull_stream(hot=hot)  # no-op once built
         if hot and hot_lds and hot_wide:
             ks, kw = hot_wide
+            if counters is not None:
+                for w, src in enumerate(part.slot_srcs):
+                    ng.pull_slots_stream_hot_queue_iter(
+                        s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
+                        src["off0"], src["hscol0"], src["n1"], src["cidx1"],
+                        src["rng1"], src["n2"], src["cidx2"], src["rng2"],
+                        src["hcol"], oldv, acc, src["lo"], src["hi"], ks, kw,
+                        counters.data_ptr() + 4 * w, max_groups)
+                return
             for src in part.slot_srcs:
                 ng.pull_slots_stream_hot_wide_iter(
                     s, src["n0"], src["cidx0"], src["nt"], src["tile0"],
@@ -992,9 +1014,20 @@ class PagerankEngine:
         # longer prefix (None: the 256-thread kernel and _hot_lds sources)
         self._hot_wide = PULL_HOT_WIDE_PREFIX \
             if self._hot_lds and pull_hot_wide_enabled() else None
+        # LUX_PULL_HOT_QUEUE: the wide sweeps take their work from a queue,
+        # one counter per src window (None: fixed roles, eight per CU)
+        self._counters = None
         if self._slots:
-            self.acc = torch.empty(max(part.na, 1), dtype=F32,
-                                   device=device)
+            # the counters sit behind acc in one buffer, so that the step's
+            # one fill clears both
+            na = max(part.na, 1)
+            queue = self._hot_wide and pull_hot_queue_enabled()
+            self._acc_buf = torch.empty(
+                na + (len(part.slot_srcs) if queue else 0), dtype=F32,
+                device=device)
+            self.acc = self._acc_buf[:na]
+            if queue:
+                self._counters = self._acc_buf[na:].view(U32)
             self.new_part = None
             # rows outside part.active hold a constant after the first
             # step; step() writes it once (again after a checkpoint resume)
@@ -1022,11 +1055,13 @@ class PagerankEngine:
     def _step_body(self):
         p = self.part
         if self._slots:
-            self.acc.zero_()
+            # inside the captured graph: every replay resets the counters
+            self._acc_buf.zero_()
             run_pull_slots_sweeps(p, self.gold if self._hot else self.old,
                                   self.acc, stream=self._stream_role,
                                   hot=self._hot, hot_lds=self._hot_lds,
-                                  hot_wide=self._hot_wide)
+                                  hot_wide=self._hot_wide,
+                                  counters=self._counters)
             # the kernel boundary after the last sweep makes the in-place
             # write safe: nothing reads `old` (or gold) until the next
             # step's sweeps

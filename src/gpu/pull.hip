@@ -24,7 +24,8 @@
 // same sweeps run on permuted column copies and a permuted rank table, and
 // lux_gpu_pull_slots_stream_hot_iter keeps a window's hottest sources in LDS
 // (lux_gpu_pull_slots_stream_hot_wide_iter: four to eight times as many, in
-// 1024-thread workgroups).
+// 1024-thread workgroups; lux_gpu_pull_slots_stream_hot_queue_iter: those on
+// the resident set, taking their work from a per-window queue).
 #include "gpu_common.h"
 
 namespace lux {
@@ -722,7 +723,8 @@ constexpr uint32_t WIDE_SCRATCH = WIDE_Q * (BLOCK / WAVE);
 // fixed role split decides the launch's tail (13.75 ms per RMAT-27 iteration
 // against 13.54 for the 256-thread kernel). Queued workgroups let dispatch
 // even the roles out and cost one more prefix copy each: 4 per CU 13.42 ms,
-// 8 per CU 13.12 ms (BENCHLOG r16.1).
+// 8 per CU 13.12 ms (BENCHLOG r16.1); 16 and 32 per CU 12.83 ms, behind the
+// queue kernel below, which is the default (r17.1).
 constexpr uint32_t WIDE_GROUPS_PER_CU = 8;
 
 template <int KS, int KW>
@@ -797,6 +799,106 @@ __global__ void __launch_bounds__(WIDE_BLOCK, 8)
     pull_stream_tiles<PR_SUM, WIDE_NW>(
         blk - s.g2 - s.g1, gridDim.x - s.g2 - s.g1, st, s.cidx0, a,
         (float(*)[TILE_EDGES])wide_lds());
+  }
+}
+
+// ---- wide hot sweep off a work queue: the resident set, roles by item ----
+// The same role bodies and row sums as pull_slots_stream_hot_wide_kernel, but
+// the grid is the two resident workgroups per CU and a workgroup takes small
+// work items from a per-launch counter instead of a fixed role and a
+// grid-stride share: chunk items first, then wave items, then stream items
+//   chunk item:  WIDE_Q * QUEUE_C hub entries (QUEUE_C per 256-thread quarter)
+//   wave item:   WIDE_NW * QUEUE_R wave-bin rows (QUEUE_R per wave)
+//   stream item: WIDE_NW * QUEUE_T tiles (QUEUE_T per wave)
+// so the prefix is copied once per workgroup and launch, and a launch ends
+// with a tail one item long. Thread 0 claims an item with one returning
+// atomicAdd and hands it to the workgroup through LDS behind the loop's one
+// barrier; the claim for the item after is issued before the current item's
+// work and waits under its gathers. A workgroup never waits for another one:
+// rows keep one writer per sweep, which is also why the queue is per window
+// (a row has slots in several windows, and their launches stay ordered).
+// One LDS layout for all roles, so a role change (at most two per launch, in
+// item order) copies nothing:
+//   prefix 0..KS-1 | upper half | 16 floats of chunk scratch
+// upper half: prefix KS..KW-1 for the chunk and wave roles, the 16 tile
+// buffers for the stream role, which gathers from the first KS sources only.
+// Item sizes, RMAT-27 sweep time per iteration (BENCHLOG r17.1): the waves of
+// a workgroup meet at a barrier per item, so short wave items wait for their
+// longest row (R = 4 / 8 / 16 / 24 / 32: 12.69 / 12.35 / 12.18 / 12.14 /
+// 12.26 ms) and long stream items lengthen the tail (T = 1 / 4 at R = 8:
+// 12.33 / 12.42); C = 1 / 2 tie. The wide kernel: 13.15 at 8 workgroups per
+// CU, 12.83 at 16 and at 32.
+constexpr uint32_t QUEUE_GROUPS_PER_CU = 2;
+constexpr uint32_t QUEUE_C = 1, QUEUE_R = 16, QUEUE_T = 1;
+
+struct WideQueue {
+  uint32_t i2, i1, total;  // items: [0, i2) chunk, [i2, i1) wave, then stream
+  uint32_t* next;          // zero before the launch
+};
+
+// New kernels keep their f32 sums in scalar adds: no packed-fp32 forms (the
+// compiler would pair a batch's accumulators). Device pass only, the host
+// pass does not know the feature.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LUX_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LUX_NO_PACKED_F32
+#endif
+
+template <int KS, int KW>
+__global__ void __launch_bounds__(WIDE_BLOCK, 8) LUX_NO_PACKED_F32
+    pull_slots_stream_hot_queue_kernel(SlotBins s, SlotStream st, PullArgs p,
+                                       V_ID lo, V_ID hi, WideQueue q) {
+  static_assert(KS + WIDE_TILE_FLOATS <= KW, "tiles overlay the upper half");
+  // two slots: thread 0 writes the next item while slower waves may still
+  // read the current one; a wave is never more than one barrier ahead
+  __shared__ uint32_t slot[2];
+  float* hot = wide_lds();
+  const float* oldv = (const float*)p.oldv;
+  uint32_t claimed = 0, par = 0;
+  if (threadIdx.x == 0) claimed = atomicAdd(q.next, 1u);
+  bool copied = false;
+  for (;; par ^= 1) {
+    if (threadIdx.x == 0) slot[par] = claimed;
+    // also: every wave is done with the LDS of the item before
+    __syncthreads();
+    uint32_t it = __builtin_amdgcn_readfirstlane(slot[par]);
+    if (it >= q.total) return;
+    if (threadIdx.x == 0) claimed = atomicAdd(q.next, 1u);
+    if (!copied) {
+      // items come in role order: a first item of the stream role means no
+      // chunk or wave item follows, and the upper half is tile buffers
+      uint32_t k = it < q.i1 ? KW : KS;
+      for (uint32_t i = threadIdx.x; i < k; i += WIDE_BLOCK) {
+        uint64_t pos = (uint64_t)lo + i;
+        hot[i] = pos < hi ? oldv[pos] : 0.0f;
+      }
+      copied = true;
+      __syncthreads();
+    }
+    // an item is the role body on a one-workgroup grid over its own range
+    if (it < q.i2) {
+      uint64_t end = ((uint64_t)it + 1) * (WIDE_Q * QUEUE_C);
+      PullArgsWide<KW, 0> a{p, lo};
+      pull_chunk_role_wide(it * QUEUE_C, 1, end < s.n2 ? (uint32_t)end : s.n2,
+                           SlotRows{s.cidx2, s.rng2}, a, hot + KW);
+    } else if (it < q.i1) {
+      uint32_t w = it - q.i2;
+      uint64_t end = ((uint64_t)w + 1) * (WIDE_NW * QUEUE_R);
+      PullArgsWide<KW, 0> a{p, lo};
+      pull_wave_role<PR_SUM>(w * QUEUE_R, 1,
+                             end < s.n1 ? (uint32_t)end : s.n1,
+                             SlotRows{s.cidx1, s.rng1}, a);
+    } else {
+      uint32_t t = it - q.i1;
+      uint64_t end = ((uint64_t)t + 1) * (WIDE_NW * QUEUE_T);
+      SlotStream sti = st;
+      if (end < st.nt) sti.nt = (uint32_t)end;
+      PullArgsWide<KS, 0> a{p, lo};
+      pull_stream_tiles<PR_SUM, WIDE_NW>(
+          t * QUEUE_T, 1, sti, s.cidx0, a,
+          (float(*)[TILE_EDGES])(hot + KW - WIDE_TILE_FLOATS));
+    }
   }
 }
 
@@ -1406,6 +1508,58 @@ int lux_gpu_pull_slots_stream_hot_wide_iter(
   } while (0)
   LUX_WIDE(8192, 16384);
 #undef LUX_WIDE
+  LUX_POST_LAUNCH(stream);
+  return 0;
+}
+
+// The wide sweep off a work queue (pull_slots_stream_hot_queue_kernel): the
+// wide entry's arguments without the edge counts (no role split), and next,
+// one u32 that is zero before the launch and is left at items + workgroups.
+// max_groups: 0 = the resident set (QUEUE_GROUPS_PER_CU per CU), else the
+// grid. Returns 0, -1 or -2 as the wide entry does (nothing is launched on
+// an error, or when no bin has an entry).
+int lux_gpu_pull_slots_stream_hot_queue_iter(
+    uint64_t stream, uint32_t n0, const V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const V_ID* scol0,
+    uint32_t n1, const V_ID* cidx1, const uint2* rng1, uint32_t n2,
+    const V_ID* cidx2, const uint2* rng2, const V_ID* col, const float* gold,
+    float* acc, V_ID lo, V_ID hi, int ks, int kw, uint32_t max_groups,
+    uint32_t* next) {
+  if (ks != 8192 || kw != 16384) return -1;
+  uint32_t g = max_groups;
+  if (!g) {
+    static const uint32_t dflt = [] {
+      int dev = 0, cus = 0;
+      if (hipGetDevice(&dev) != hipSuccess ||
+          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                dev) != hipSuccess)
+        return 0u;
+      return (uint32_t)(QUEUE_GROUPS_PER_CU * cus);
+    }();
+    if (!dflt) return -2;
+    g = dflt;
+  }
+  auto items = [](uint32_t n, uint32_t per) {
+    return (uint32_t)(((uint64_t)n + per - 1) / per);
+  };
+  if (!(n0 && nt)) nt = 0;
+  WideQueue q{items(n2, WIDE_Q * QUEUE_C), 0, 0, next};
+  q.i1 = q.i2 + items(n1, WIDE_NW * QUEUE_R);
+  q.total = q.i1 + items(nt, WIDE_NW * QUEUE_T);
+  if (!q.total) return 0;
+  SlotBins sb{n0, n1, n2, 0, 0, cidx0, cidx1, cidx2, nullptr, rng1, rng2};
+  SlotStream st{nt, tile0, off0, scol0};
+  PullArgs a{nullptr, col, gold, acc, nullptr, 0, 0.0f};
+  auto kern = pull_slots_stream_hot_queue_kernel<8192, 16384>;
+  // the static part of the kernel's LDS is the two item slots
+  constexpr uint32_t bytes = wide_lds_bytes<8192, 16384>();
+  static_assert(2 * (bytes + 8) <= 160 * 1024, "two workgroups per CU");
+  static const hipError_t raised = hipFuncSetAttribute(
+      (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (int)bytes);
+  if (raised != hipSuccess) return -2;
+  hipLaunchKernelGGL(kern, dim3(g), dim3(WIDE_BLOCK), bytes,
+                     (hipStream_t)stream, sb, st, a, lo, hi, q);
   LUX_POST_LAUNCH(stream);
   return 0;
 }

@@ -191,6 +191,17 @@ int lux_gpu_pull_slots_stream_hot_wide_iter(
     uint32_t n2, const lux::V_ID* cidx2, const lux_uint2* rng2,
     const lux::V_ID* col, uint64_t ne, const float* gold, float* acc,
     lux::V_ID lo, lux::V_ID hi, int ks, int kw, uint32_t max_groups);
+// the wide sweep on the resident set (two workgroups per CU), the workgroups
+// taking small work items of the three roles from a queue. next: one u32,
+// zero before the launch. max_groups: 0 = the resident set, else the grid
+// size. Same return codes.
+int lux_gpu_pull_slots_stream_hot_queue_iter(
+    uint64_t stream, uint32_t n0, const lux::V_ID* cidx0, uint32_t nt,
+    const uint32_t* tile0, const uint32_t* off0, const lux::V_ID* scol0,
+    uint32_t n1, const lux::V_ID* cidx1, const lux_uint2* rng1, uint32_t n2,
+    const lux::V_ID* cidx2, const lux_uint2* rng2, const lux::V_ID* col,
+    const float* gold, float* acc, lux::V_ID lo, lux::V_ID hi, int ks, int kw,
+    uint32_t max_groups, uint32_t* next);
 void lux_gpu_pull_fill_inactive_pr(uint64_t stream, lux::V_ID vp,
                                    const lux::E_ID* row_ptr, float* out,
                                    const lux::V_ID* deg, lux::V_ID row_left,
