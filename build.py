@@ -30,6 +30,13 @@ HIPFLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INC}",
     "-Wall", "-Wno-unused-function",
 ]
+# per-source additions: kernels added from truss.hip on are compiled with
+# the packed fp32 instructions off (the older objects keep their flags, so
+# their code does not change)
+HIPFLAGS_EXTRA = {
+    "truss.hip": ["-Xclang", "-target-feature", "-Xclang",
+                  "-packed-fp32-ops"],
+}
 
 
 def _newer(target, deps):
@@ -63,7 +70,8 @@ def build_gpu(force=False):
         for s in GPU_SRCS:
             obj = s.replace(".hip", ".o")
             if _newer(obj, [s] + hdrs) or force:
-                _run([HIPCC, "-c", *HIPFLAGS, s, "-o", obj])
+                extra = HIPFLAGS_EXTRA.get(os.path.basename(s), [])
+                _run([HIPCC, "-c", *HIPFLAGS, *extra, s, "-o", obj])
             objs.append(obj)
         _run([HIPCC, "-shared", *HIPFLAGS, *objs, "-o", GPU_LIB])
     return GPU_LIB

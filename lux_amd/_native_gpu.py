@@ -641,6 +641,83 @@ def kcore_check(stream, nv, aptr, aadj, core, bad):
                               dp(core), dp(bad))
 
 
+# ---- k-truss decomposition (truss.hip) ----
+
+class TrussArgs(ctypes.Structure):
+    """lux_truss_args: the adjacency with edge ids, the peel state and the
+    list range [head, tail) of one launch."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "aptr", "aadj", "aeid", "elo", "ehi", "sup", "sup0", "order", "pos",
+        "truss", "hubq", "meta", "bad")] + \
+        [(n, ctypes.c_uint32) for n in ("m", "hubcap", "hub", "fence")] + \
+        [("s", ctypes.c_int), ("head", ctypes.c_uint32),
+         ("tail", ctypes.c_uint32)]
+
+
+TRUSS_SUPPORT, TRUSS_PEEL, TRUSS_CHECK = 0, 1, 2
+# meta words
+(TRUSS_M_TAIL, TRUSS_M_HUBTAIL, TRUSS_M_MIN, TRUSS_M_FUSED, TRUSS_M_HEAD,
+ TRUSS_M_LANE, TRUSS_M_WAVE) = range(7)
+
+
+def truss_const(what):
+    """what: hub_default, fuse_default, fuse_max, fence_default, fence_max
+    or meta_words (truss.hip's TRUSS_* constants)."""
+    f = getattr(lib(), f"lux_gpu_truss_{what}")
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def truss_args(m, hubcap, hub, fence, **tensors):
+    """Tensors by field name; a field left out is a null pointer."""
+    a = TrussArgs()
+    for name, t in tensors.items():
+        setattr(a, name, t.data_ptr())
+    a.m, a.hubcap, a.hub, a.fence = m, hubcap, hub, fence
+    return a
+
+
+def truss_adj_fill(stream, nv, m, optr, oadj, keys, base, aadj, aeid, elo):
+    """keys: a run of the sorted directed keys, entries base.. of the
+    adjacency."""
+    lib().lux_gpu_truss_adj_fill(_u64(stream), _u32(nv), _u64(m), dp(optr),
+                                 dp(oadj), dp(keys), _u64(keys.numel()),
+                                 _u64(base), dp(aadj), dp(aeid), dp(elo))
+
+
+def _truss_call(name, rc, a):
+    if rc != 0:
+        raise ValueError(f"{name}: bad launch [{a.head}, {a.tail}) of "
+                         f"m={a.m}, hub={a.hub}, fence={a.fence}, "
+                         f"hubcap={a.hubcap}")
+
+
+def truss_classify(stream, a, fill):
+    _truss_call("truss_classify", lib().lux_gpu_truss_classify(
+        _u64(stream), ctypes.byref(a), ctypes.c_int(fill)), a)
+
+
+def truss_scan(stream, a, s):
+    a.s = s
+    _truss_call("truss_scan", lib().lux_gpu_truss_scan(
+        _u64(stream), ctypes.byref(a)), a)
+
+
+def truss_round(stream, a, mode, head, tail, hubhead, hubtail, s=0):
+    """order[head:tail) and the hubq items [hubhead, hubtail) in one mode."""
+    a.head, a.tail, a.s = head, tail, s
+    _truss_call("truss_round", lib().lux_gpu_truss_round(
+        _u64(stream), ctypes.byref(a), ctypes.c_int(mode), _u32(hubhead),
+        _u32(hubtail)), a)
+
+
+def truss_tail(stream, a, s, head, tail, hubtail, fuse):
+    """Small rounds of level s from order[head:tail) on, one workgroup."""
+    a.head, a.tail, a.s = head, tail, s
+    _truss_call("truss_tail", lib().lux_gpu_truss_tail(
+        _u64(stream), ctypes.byref(a), _u32(hubtail), _u32(fuse)), a)
+
+
 # ---- strongly connected components (scc.hip) ----
 
 class SccArgs(ctypes.Structure):

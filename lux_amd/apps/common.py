@@ -34,6 +34,7 @@ class AppArgs:
         self.order = "degree"  # tc: vertex order of the orientation
         #                        (degree | id)
         self.kcore = None  # kcore: also report the size of this K-core
+        self.truss = None  # truss: also report the size of this K-truss
 
 
 def parse_input_args(argv):
@@ -75,6 +76,8 @@ def parse_input_args(argv):
             a.order = argv[i + 1]; i += 2
         elif f == "-kcore":
             a.kcore = int(argv[i + 1]); i += 2
+        elif f == "-truss":
+            a.truss = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

@@ -420,6 +420,63 @@ void lux_gpu_kcore_check(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
                          const lux::V_ID* aadj, const int* core,
                          unsigned long long* bad);
 
+// truss.hip (k-truss decomposition by decremental peeling, single rank).
+// optr / oadj: the id-order DAG, arc e = edge e. aptr u64[nv+1] / aadj
+// u32[2m] / aeid u32[2m]: the full adjacency, rows strictly ascending, with
+// the edge id of every entry; elo / ehi u32[m]: the endpoints. A launch
+// works on order[head : tail) (a list of edge ids: a peel round, or a role
+// list of the classification) and the hubq items [hubhead, hubtail)
+// ({edge, chunk} u32 pairs, hubcap of them). meta u32[meta_words]: [0] the
+// order cursor, [1] the hubq cursor, [2] the scan's min{sup : sup > s}
+// (0xFFFFFFFF: none), [3] rounds done and [4] first unprocessed entry of
+// the last tail launch, [5] / [6] the classification's lane / wave counts.
+// hub: an edge whose shorter row is longer than this goes through hubq, in
+// chunks of hub entries; fence: entries of the hub role's LDS table.
+struct lux_truss_args {
+  const lux::E_ID* aptr;
+  const lux::V_ID* aadj;
+  const uint32_t* aeid;
+  const lux::V_ID* elo;
+  const lux::V_ID* ehi;
+  int* sup;                 // i32[m], the current support
+  const int* sup0;          // i32[m], the support of the whole graph (check)
+  uint32_t* order;          // u32[m]
+  uint32_t* pos;            // u32[m], 0xFFFFFFFF = not queued
+  uint32_t* truss;          // u32[m]
+  uint32_t* hubq;           // u32 pairs
+  uint32_t* meta;           // u32[meta_words]
+  unsigned long long* bad;  // one u64, added to by the check
+  uint32_t m, hubcap, hub, fence;
+  int s;                    // the level: edges of support <= s leave
+  uint32_t head, tail;
+};
+uint32_t lux_gpu_truss_hub_default();
+uint32_t lux_gpu_truss_fuse_default();
+uint32_t lux_gpu_truss_fuse_max();
+uint32_t lux_gpu_truss_fence_default();
+uint32_t lux_gpu_truss_fence_max();
+uint32_t lux_gpu_truss_meta_words();
+// keys[0 : n): entries base.. of the sorted directed keys (a << 32) | b.
+void lux_gpu_truss_adj_fill(uint64_t stream, lux::V_ID nv, lux::E_ID m,
+                            const lux::E_ID* optr, const lux::V_ID* oadj,
+                            const unsigned long long* keys, uint64_t n,
+                            uint64_t base, lux::V_ID* aadj, uint32_t* aeid,
+                            lux::V_ID* elo);
+// The entries below return -1 (and launch nothing) on arguments out of
+// order or beyond the lists. classify: count the roles of all m edges in
+// meta[5], meta[6] and meta[1], and with fill list them (lane edges from
+// the front of order, wave edges from its back, hub items in hubq). round:
+// mode 0 support / 1 peel / 2 check. tail: rounds of level s from
+// order[head : tail) on, one workgroup, while they hold at most fuse
+// entries and no hub edge (hubtail: the hubq cursor at launch).
+int lux_gpu_truss_classify(uint64_t stream, const lux_truss_args* a,
+                           int fill);
+int lux_gpu_truss_scan(uint64_t stream, const lux_truss_args* a);
+int lux_gpu_truss_round(uint64_t stream, const lux_truss_args* a, int mode,
+                        uint32_t hubhead, uint32_t hubtail);
+int lux_gpu_truss_tail(uint64_t stream, const lux_truss_args* a,
+                       uint32_t hubtail, uint32_t fuse);
+
 // scc.hip (strongly connected components: trim, forward-backward reach and
 // colour propagation; single rank). lux_scc_args is the graph in both
 // directions and the per-vertex state, lux_scc_step one frontier step or
