@@ -36,6 +36,8 @@ HIPFLAGS = [
 HIPFLAGS_EXTRA = {
     "truss.hip": ["-Xclang", "-target-feature", "-Xclang",
                   "-packed-fp32-ops"],
+    "lpa.hip": ["-Xclang", "-target-feature", "-Xclang",
+                "-packed-fp32-ops"],
 }
 
 

@@ -372,6 +372,40 @@ def greedy_colouring_cpu(nv, ne, col_end, src, order, seed):
     return colour
 
 
+def label_propagation_cpu(nv, ne, col_end, src, order, seed, init,
+                          max_sweeps):
+    """(label i32[nv], [(sweep, evaluated, changed)]) of the sequential
+    label propagation in (colour, id) order."""
+    if order not in COLOURING_ORDERS:
+        raise ValueError(f"order must be one of {COLOURING_ORDERS}, "
+                         f"got {order!r}")
+    if init is not None:
+        init = np.ascontiguousarray(init, np.int32)
+        if init.shape != (nv,):
+            raise ValueError(f"init must have shape ({nv},), "
+                             f"got {init.shape}")
+    label = np.empty(nv, np.int32)
+    cpu.lux_label_propagation_cpu.restype = ctypes.c_int64
+    cap = 1024
+    while True:
+        trace = np.zeros(2 * cap, np.uint64)
+        n = int(cpu.lux_label_propagation_cpu(
+            ctypes.c_uint32(nv), ctypes.c_uint64(ne), ptr(col_end, u64p),
+            ptr(src, u32p), ctypes.c_int(COLOURING_ORDERS.index(order)),
+            ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            ptr(init, i32p), ctypes.c_uint64(max(int(max_sweeps), 0)),
+            ptr(label, i32p), ptr(trace, u64p), ctypes.c_uint64(cap)))
+        if n == -2:
+            raise ValueError(f"init labels must lie in [0, {nv})")
+        if n < 0:
+            raise ValueError(f"label_propagation_cpu: bad order {order!r}")
+        if n <= cap:
+            break
+        cap = n  # a longer run than the trace buffer: once more
+    return label, [(i + 1, int(trace[2 * i]), int(trace[2 * i + 1]))
+                   for i in range(n)]
+
+
 def scc_cpu(nv, ne, col_end, src):
     """label u32[nv]: the largest vertex id of each vertex's SCC."""
     label = np.empty(nv, np.uint32)

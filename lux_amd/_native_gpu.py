@@ -1040,3 +1040,88 @@ def gcol_tail(stream, a, head, tail, hubtail, fuse, round0):
 def gcol_check(stream, nv, pptr, padj, sptr, sadj, colour, bad):
     lib().lux_gpu_gcol_check(_u64(stream), _u32(nv), dp(pptr), dp(padj),
                              dp(sptr), dp(sadj), dp(colour), dp(bad))
+
+
+# ---- community detection by label propagation (lpa.hip) ----
+
+class LpaArgs(ctypes.Structure):
+    """lux_lpa_args: the adjacency, the class order, the hub items and the
+    state of a solve."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "aptr", "aadj", "vorder", "cptr", "label", "dirty", "hubv", "hubp",
+        "hubr", "hptr", "hubkey", "hubdone", "meta", "bad")] + \
+        [(n, ctypes.c_uint32) for n in (
+            "nv", "ncls", "nitems", "nhub", "hub", "table")]
+
+
+# meta words
+LPA_M_EVAL, LPA_M_CHANGED = range(2)
+
+
+def lpa_hub_default():
+    """LPA_HUB: the longest table-role row when LUX_LPA_HUB is unset."""
+    return _gcol_const("lux_gpu_lpa_hub_default")
+
+
+def lpa_table_default():
+    """LPA_TABLE: the slots of the LDS table when LUX_LPA_TABLE is unset."""
+    return _gcol_const("lux_gpu_lpa_table_default")
+
+
+def lpa_table_range():
+    return (_gcol_const("lux_gpu_lpa_table_min"),
+            _gcol_const("lux_gpu_lpa_table_max"))
+
+
+def lpa_fuse_default():
+    """LPA_FUSE: the vertices of a fused launch when LUX_LPA_FUSE is
+    unset."""
+    return _gcol_const("lux_gpu_lpa_fuse_default")
+
+
+def lpa_fuse_max():
+    return _gcol_const("lux_gpu_lpa_fuse_max")
+
+
+def lpa_meta_words():
+    return _gcol_const("lux_gpu_lpa_meta_words")
+
+
+def lpa_row_limit(hub, table):
+    """The longest row the table role takes at these knobs: hub, but no more
+    than a wave's quarter of the table holds at half load, and at least
+    64."""
+    f = lib().lux_gpu_lpa_row_limit
+    f.restype = ctypes.c_uint32
+    return int(f(_u32(hub), _u32(table)))
+
+
+def lpa_args(aptr, aadj, vorder, cptr, label, dirty, hubv, hubp, hubr, hptr,
+             hubkey, hubdone, meta, bad, nv, ncls, nitems, nhub, hub, table):
+    return LpaArgs(*(t.data_ptr() for t in (
+        aptr, aadj, vorder, cptr, label, dirty, hubv, hubp, hubr, hptr,
+        hubkey, hubdone, meta, bad)), nv, ncls, nitems, nhub, hub, table)
+
+
+def lpa_classes(stream, a, c0, c1, nrows, nitems, maxdeg, fused):
+    """Evaluate classes [c0, c1): nrows entries of vorder, the longest row
+    maxdeg, nitems hub items; fused: one workgroup, class after class."""
+    rc = lib().lux_gpu_lpa_classes(_u64(stream), ctypes.byref(a), _u32(c0),
+                                   _u32(c1), _u32(nrows), _u32(nitems),
+                                   _u32(maxdeg), ctypes.c_int(int(fused)))
+    if rc != 0:
+        raise ValueError(f"lpa_classes: rc={rc} for classes [{c0}, {c1}), "
+                         f"{nrows} rows, {nitems} items, fused={fused}, "
+                         f"hub={a.hub}, table={a.table}")
+
+
+def lpa_check(stream, a):
+    rc = lib().lux_gpu_lpa_check(_u64(stream), ctypes.byref(a))
+    if rc != 0:
+        raise ValueError(f"lpa_check: rc={rc}, hub={a.hub}, "
+                         f"table={a.table}")
+
+
+def lpa_stats(stream, nv, aptr, aadj, label, sizes, tot, intra):
+    lib().lux_gpu_lpa_stats(_u64(stream), _u32(nv), dp(aptr), dp(aadj),
+                            dp(label), dp(sizes), dp(tot), dp(intra))

@@ -130,6 +130,51 @@ def greedy_colouring(g: Graph, order="degree", seed=1) -> np.ndarray:
                                     seed)
 
 
+def label_propagation(g: Graph, order="degree", seed=1, init=None,
+                      max_sweeps=0):
+    """(labels i32[nv], [(sweep, evaluated, changed)]) on the simple
+    undirected graph of triangles(): semi-synchronous label propagation, the
+    sequential pass in (greedy_colouring(order, seed), id) order of API.md.
+    label[v] starts as v or init[v]; a dirty vertex with a neighbour takes
+    the smallest most frequent label of its neighbours unless its own is as
+    frequent, and then marks its neighbours dirty. Ends after the first
+    sweep without a change, or after max_sweeps sweeps if max_sweeps > 0.
+    C++, one sequential loop sorting each row; no roles, no tables, no
+    classes."""
+    return nat.label_propagation_cpu(g.nv, g.ne, g.col_end, g.src, order,
+                                     seed, init, max_sweeps)
+
+
+def modularity(intra, m, tot):
+    """intra / m - sum(tot[l]^2) / (4 m^2) from exact integers (tot: an
+    iterable of ints), 0.0 for m == 0."""
+    from fractions import Fraction
+    if m == 0:
+        return 0.0
+    return float(Fraction(int(intra), m) -
+                 Fraction(sum(int(t) * int(t) for t in tot), 4 * m * m))
+
+
+def community_stats(g: Graph, labels):
+    """dict(m, sizes i64[nv], tot i64[nv], intra, modularity) of a labelling
+    of the simple undirected graph of triangles(): the vertices and the
+    degree sum per label id, and the simple edges inside a community."""
+    dst = np.repeat(np.arange(g.nv, dtype=np.int64),
+                    np.diff(np.concatenate(([0], g.col_end)).astype(np.int64)))
+    s = g.src.astype(np.int64)
+    keep = s != dst
+    e = np.unique(np.minimum(s, dst)[keep] * g.nv + np.maximum(s, dst)[keep])
+    lo, hi = e // max(g.nv, 1), e % max(g.nv, 1)
+    m = int(e.size)
+    lab = np.asarray(labels, np.int64)
+    deg = np.bincount(lo, minlength=g.nv) + np.bincount(hi, minlength=g.nv)
+    tot = np.zeros(g.nv, np.int64)
+    np.add.at(tot, lab, deg)
+    intra = int((lab[lo] == lab[hi]).sum())
+    return dict(m=m, sizes=np.bincount(lab, minlength=g.nv), tot=tot,
+                intra=intra, modularity=modularity(intra, m, tot[tot > 0]))
+
+
 def scc(g: Graph) -> np.ndarray:
     """label u32[nv] of the directed graph as loaded (row v of the CSC lists
     the sources u of the edges u -> v; parallel edges and self-loops change

@@ -45,6 +45,11 @@ void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
 int greedy_colouring_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
                          const V_ID* src, int order, uint64_t seed,
                          int32_t* colour);
+int64_t label_propagation_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
+                              const V_ID* src, int order, uint64_t seed,
+                              const int32_t* init, uint64_t max_sweeps,
+                              int32_t* label, uint64_t* trace,
+                              uint64_t trace_cap);
 void scc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
              uint32_t* label);
 E_ID msf_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
@@ -276,6 +281,18 @@ int lux_greedy_colouring_cpu(uint32_t nv, uint64_t ne,
                              const uint64_t* col_end, const uint32_t* src,
                              int order, uint64_t seed, int32_t* colour) {
   return greedy_colouring_cpu(nv, ne, col_end, src, order, seed, colour);
+}
+// order / seed as above; init i32[nv] or null; label i32[nv]; trace
+// u64[2 * trace_cap]: {evaluated, changed} of the first trace_cap sweeps.
+// Returns the sweeps, -1 on an unknown order, -2 on a bad init label.
+int64_t lux_label_propagation_cpu(uint32_t nv, uint64_t ne,
+                                  const uint64_t* col_end,
+                                  const uint32_t* src, int order,
+                                  uint64_t seed, const int32_t* init,
+                                  uint64_t max_sweeps, int32_t* label,
+                                  uint64_t* trace, uint64_t trace_cap) {
+  return label_propagation_cpu(nv, ne, col_end, src, order, seed, init,
+                               max_sweeps, label, trace, trace_cap);
 }
 void lux_scc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                  const uint32_t* src, uint32_t* label) {

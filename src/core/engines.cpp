@@ -625,6 +625,90 @@ int greedy_colouring_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
   return 0;
 }
 
+// ---------- label propagation ----------
+// Exact oracle of LPAEngine (no reference equivalent), on the same simple
+// undirected graph as tc_cpu: semi-synchronous label propagation in the
+// fixed order (colour, id), colour = greedy_colouring_cpu(order, seed). One
+// sequential loop: a vertex with deg > 0 and dirty set clears dirty, sorts
+// its neighbours' labels, and unless its own label reaches the largest count
+// takes the smallest label that does and marks its neighbours dirty. init:
+// nv labels in [0, nv) or null (label[v] = v). Stops after the first sweep
+// without a change, or after max_sweeps sweeps if max_sweeps > 0. trace:
+// {evaluated, changed} per sweep, the first trace_cap sweeps. Returns the
+// number of sweeps, -1 on an unknown order, -2 on a label outside [0, nv).
+int64_t label_propagation_cpu(V_ID nv, E_ID ne, const E_ID* col_end,
+                              const V_ID* src, int order, uint64_t seed,
+                              const int32_t* init, uint64_t max_sweeps,
+                              int32_t* label, uint64_t* trace,
+                              uint64_t trace_cap) {
+  std::vector<int32_t> colour(nv);
+  if (greedy_colouring_cpu(nv, ne, col_end, src, order, seed,
+                           colour.data()) != 0)
+    return -1;
+  std::vector<std::vector<V_ID>> nbr(nv);
+  E_ID b = 0;
+  for (V_ID v = 0; v < nv; v++) {
+    for (E_ID i = b; i < col_end[v]; i++) {
+      V_ID s = src[i];
+      if (s == v || s >= nv) continue;
+      nbr[v].push_back(s);
+      nbr[s].push_back(v);
+    }
+    b = col_end[v];
+  }
+  for (V_ID v = 0; v < nv; v++) {
+    std::sort(nbr[v].begin(), nbr[v].end());
+    nbr[v].erase(std::unique(nbr[v].begin(), nbr[v].end()), nbr[v].end());
+  }
+  std::vector<V_ID> seq(nv);
+  for (V_ID v = 0; v < nv; v++) seq[v] = v;
+  std::stable_sort(seq.begin(), seq.end(), [&](V_ID x, V_ID y) {
+    return colour[x] < colour[y];
+  });
+  for (V_ID v = 0; v < nv; v++) {
+    label[v] = init ? init[v] : (int32_t)v;
+    if (label[v] < 0 || (uint32_t)label[v] >= nv) return -2;
+  }
+  std::vector<uint8_t> dirty(nv, 1);
+  std::vector<int32_t> row;
+  uint64_t sweeps = 0;
+  for (;;) {
+    uint64_t evaluated = 0, changed = 0;
+    for (V_ID k = 0; k < nv; k++) {
+      V_ID v = seq[k];
+      if (nbr[v].empty() || !dirty[v]) continue;
+      dirty[v] = 0;
+      evaluated++;
+      row.clear();
+      for (V_ID u : nbr[v]) row.push_back(label[u]);
+      std::sort(row.begin(), row.end());
+      size_t best = 0, mine = 0;
+      int32_t best_label = -1;
+      for (size_t i = 0; i < row.size();) {
+        size_t j = i;
+        while (j < row.size() && row[j] == row[i]) j++;
+        if (j - i > best) {  // ascending labels: the smallest one is kept
+          best = j - i;
+          best_label = row[i];
+        }
+        if (row[i] == label[v]) mine = j - i;
+        i = j;
+      }
+      if (mine == best) continue;
+      label[v] = best_label;
+      changed++;
+      for (V_ID u : nbr[v]) dirty[u] = 1;
+    }
+    if (sweeps < trace_cap) {
+      trace[2 * sweeps] = evaluated;
+      trace[2 * sweeps + 1] = changed;
+    }
+    sweeps++;
+    if (changed == 0 || (max_sweeps && sweeps >= max_sweeps)) break;
+  }
+  return (int64_t)sweeps;
+}
+
 // ---------- strongly connected components ----------
 // Exact oracle of SCCEngine (no reference equivalent), on the directed graph
 // as loaded: row v of the CSC lists the sources u of the edges u -> v.

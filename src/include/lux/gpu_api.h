@@ -655,4 +655,52 @@ void lux_gpu_gcol_check(uint64_t stream, lux::V_ID nv, const lux::E_ID* pptr,
                         const lux::V_ID* sadj, const int* colour,
                         unsigned long long* bad);
 
+// lpa.hip (community detection by colour-class label propagation; single
+// rank). aptr / aadj: the full symmetric adjacency of kcore_adj_fill. vorder:
+// the vertices sorted by (colour, id), cptr: the class offsets into it. hub
+// items are {hubv, hubp, hubr} = {vertex, pass, hub row}, one per pass
+// p < ceil(deg / (table / 2)) of every row longer than hub, in class order;
+// hptr: the class offsets into them. hubkey / hubdone: one word per hub row,
+// zero between sweeps. meta u32[meta_words]: [0] evaluated and [1] changed
+// rows, added to. hub is the longest table-role row, lux_gpu_lpa_row_limit of
+// the knobs.
+struct lux_lpa_args {
+  const lux::E_ID* aptr;       // u64[nv+1]
+  const lux::V_ID* aadj;       // u32[2m]
+  const lux::V_ID* vorder;     // u32[nv]
+  const uint32_t* cptr;        // u32[ncls+1]
+  int* label;                  // i32[nv]
+  uint32_t* dirty;             // u32[nv], 0 / 1
+  const lux::V_ID* hubv;       // u32[nitems]
+  const uint32_t* hubp;        // u32[nitems]
+  const uint32_t* hubr;        // u32[nitems]
+  const uint32_t* hptr;        // u32[ncls+1]
+  unsigned long long* hubkey;  // u64[nhub]
+  uint32_t* hubdone;           // u32[nhub]
+  uint32_t* meta;              // u32[meta_words]
+  unsigned long long* bad;     // one u64 (check mode)
+  lux::V_ID nv;
+  uint32_t ncls;
+  uint32_t nitems;
+  uint32_t nhub;
+  uint32_t hub;    // rows longer than this go through hub items
+  uint32_t table;  // slots of the LDS table, a power of two
+};
+uint32_t lux_gpu_lpa_hub_default();
+uint32_t lux_gpu_lpa_table_default();
+uint32_t lux_gpu_lpa_table_min();
+uint32_t lux_gpu_lpa_table_max();
+uint32_t lux_gpu_lpa_fuse_default();
+uint32_t lux_gpu_lpa_fuse_max();
+uint32_t lux_gpu_lpa_meta_words();
+uint32_t lux_gpu_lpa_row_limit(uint32_t hub, uint32_t table);
+int lux_gpu_lpa_classes(uint64_t stream, const lux_lpa_args* a, uint32_t c0,
+                        uint32_t c1, uint32_t nrows, uint32_t nitems,
+                        uint32_t maxdeg, int fused);
+int lux_gpu_lpa_check(uint64_t stream, const lux_lpa_args* a);
+void lux_gpu_lpa_stats(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
+                       const lux::V_ID* aadj, const int* label,
+                       unsigned long long* sizes, unsigned long long* tot,
+                       unsigned long long* intra);
+
 }  // extern "C"
