@@ -1125,3 +1125,87 @@ def lpa_check(stream, a):
 def lpa_stats(stream, nv, aptr, aadj, label, sizes, tot, intra):
     lib().lux_gpu_lpa_stats(_u64(stream), _u32(nv), dp(aptr), dp(aadj),
                             dp(label), dp(sizes), dp(tot), dp(intra))
+
+
+# ---- bit-parallel multi-source BFS (msbfs.hip) ----
+
+class MsbfsArgs(ctypes.Structure):
+    """lux_msbfs_args: both edge directions, the per-vertex words and sums,
+    the static pull role lists and the push queues."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "in_ptr", "in_col", "out_ptr", "out_col", "seen", "front", "next",
+        "dist_sum", "harmonic", "reach", "thr_in", "wav_in", "hub_in",
+        "qthr", "qwav", "qhub", "meta")] + \
+        [(n, ctypes.c_uint32) for n in (
+            "nv", "n_thr_in", "n_wav_in", "n_hub_in", "hubcap_out", "hub",
+            "thr")]
+
+
+# meta words (u64)
+(MSBFS_M_FRONT, MSBFS_M_VOLUME, MSBFS_M_PAIRS, MSBFS_M_NTHR, MSBFS_M_NWAV,
+ MSBFS_M_NHUB, MSBFS_M_SCANNED, _, MSBFS_M_SRC) = range(9)
+MSBFS_BATCH = 64
+
+
+def msbfs_hub_default():
+    """MSBFS_HUB: the longest wave-role row when LUX_MSBFS_HUB is unset."""
+    return _gcol_const("lux_gpu_msbfs_hub_default")
+
+
+def msbfs_hub_max():
+    return _gcol_const("lux_gpu_msbfs_hub_max")
+
+
+def msbfs_thread_limit():
+    """MSBFS_THREAD: the longest row a single lane takes."""
+    return _gcol_const("lux_gpu_msbfs_thread_limit")
+
+
+def msbfs_pull_div_default():
+    """MSBFS_PULL_DIV: the divisor of the direction rule when
+    LUX_MSBFS_PULL_DIV is unset."""
+    return _gcol_const("lux_gpu_msbfs_pull_div_default")
+
+
+def msbfs_meta_words():
+    return _gcol_const("lux_gpu_msbfs_meta_words")
+
+
+def msbfs_args(tensors, nv, n_thr_in, n_wav_in, n_hub_in, hubcap_out, hub,
+               thr):
+    """tensors: the 17 device arrays in the struct's order."""
+    return MsbfsArgs(*(t.data_ptr() for t in tensors), nv, n_thr_in,
+                     n_wav_in, n_hub_in, hubcap_out, hub, thr)
+
+
+def _msbfs_rc(name, rc, a):
+    if rc != 0:
+        raise ValueError(f"{name}: rc={rc}, nv={a.nv}, hub={a.hub}, "
+                         f"thr={a.thr}, hubcap_out={a.hubcap_out}")
+
+
+def msbfs_seed(stream, a, sources, k):
+    _msbfs_rc("msbfs_seed", lib().lux_gpu_msbfs_seed(
+        _u64(stream), ctypes.byref(a), dp(sources), _u32(k)), a)
+
+
+def msbfs_pull(stream, a, active):
+    _msbfs_rc("msbfs_pull", lib().lux_gpu_msbfs_pull(
+        _u64(stream), ctypes.byref(a), _u64(active)), a)
+
+
+def msbfs_push(stream, a, nthr, nwav, nhub):
+    _msbfs_rc(f"msbfs_push({nthr}, {nwav}, {nhub})",
+              lib().lux_gpu_msbfs_push(_u64(stream), ctypes.byref(a),
+                                       _u32(nthr), _u32(nwav), _u32(nhub)), a)
+
+
+def msbfs_epilogue(stream, a, d, k, depth):
+    _msbfs_rc("msbfs_epilogue", lib().lux_gpu_msbfs_epilogue(
+        _u64(stream), ctypes.byref(a), _u32(d), _u32(k), dp(depth)), a)
+
+
+def msbfs_check(stream, a, seen, depth, sources, k, bad):
+    _msbfs_rc("msbfs_check", lib().lux_gpu_msbfs_check(
+        _u64(stream), ctypes.byref(a), dp(seen), dp(depth), dp(sources),
+        _u32(k), dp(bad)), a)

@@ -175,6 +175,54 @@ def community_stats(g: Graph, labels):
                 intra=intra, modularity=modularity(intra, m, tot[tot > 0]))
 
 
+def multi_source_bfs(g: Graph, sources) -> np.ndarray:
+    """i32[k, nv]: the hop distance from each source along the edges
+    u -> v of the directed graph as loaded, -1 where unreached. One call of
+    the sssp hop oracle per source."""
+    out = np.empty((len(sources), g.nv), np.int32)
+    for i, s in enumerate(sources):
+        out[i] = sssp(g, int(s))[0].view(np.int32)  # INF is -1
+    return out
+
+
+def multi_source_stats(g: Graph, sources, div=8, batch=64):
+    """What MSBFSEngine reports, from multi_source_bfs with plain numpy in
+    the order API.md defines: dict(depths, reach, dist_sum, harmonic,
+    level_counts, reached, farness, eccentricity, closeness, level_trace).
+    harmonic is accumulated batch by batch, level by level, one division and
+    one addition per vertex and level. level_trace: (batch, level, direction,
+    frontier, volume, new_pairs) with the direction the rule
+    volume * div > ne gives."""
+    depths = multi_source_bfs(g, sources)
+    k, nv = depths.shape
+    outdeg = g.out_degrees().astype(np.int64)
+    hit = depths >= 0
+    harmonic = np.zeros(nv, np.float64)
+    trace = []
+    for b in range(0, k, batch):
+        d = depths[b:b + batch]
+        for level in range(int(d.max()) + 1):
+            new = (d == level).sum(0)
+            if level:
+                harmonic[new > 0] += new[new > 0] / np.float64(level)
+            volume = int(outdeg[new > 0].sum())
+            trace.append((b // batch, level,
+                          "pull" if volume * div > g.ne else "push",
+                          int((new > 0).sum()), volume, int(new.sum())))
+    counts = [np.bincount(row[row >= 0]).tolist() for row in depths]
+    reached = np.array([sum(c) for c in counts], np.int64)
+    farness = np.array([sum(i * n for i, n in enumerate(c)) for c in counts],
+                       np.int64)
+    closeness = np.divide(reached - 1.0, farness, where=farness > 0,
+                          out=np.zeros(k, np.float64))
+    return dict(depths=depths, reach=hit.sum(0).astype(np.int32),
+                dist_sum=np.where(hit, depths, 0).sum(0, dtype=np.int64),
+                harmonic=harmonic, level_counts=counts, reached=reached,
+                farness=farness,
+                eccentricity=np.array([len(c) - 1 for c in counts], np.int64),
+                closeness=closeness, level_trace=trace)
+
+
 def scc(g: Graph) -> np.ndarray:
     """label u32[nv] of the directed graph as loaded (row v of the CSC lists
     the sources u of the edges u -> v; parallel edges and self-loops change

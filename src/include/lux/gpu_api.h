@@ -703,4 +703,60 @@ void lux_gpu_lpa_stats(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
                        unsigned long long* sizes, unsigned long long* tot,
                        unsigned long long* intra);
 
+// msbfs.hip (bit-parallel multi-source BFS, 64 sources per word; single
+// rank). in_ptr / in_col: the CSC, out_ptr / out_col: the out-edge CSR.
+// seen / front / next: one word per vertex, bit i = source i of the batch.
+// thr_in / wav_in: the vertices of in-degree [1, thr] and (thr, hub];
+// hub_in: the {vertex, chunk} pairs of the rows longer than hub. qthr / qwav
+// (u32[nv] each) and qhub ({vertex, chunk} pairs, hubcap_out of them) are the
+// frontier by out-degree role, written by the epilogue; their tails are meta
+// words. meta u64[meta_words]: [0] frontier vertices, [1] their out-degree
+// sum, [2] new (source, vertex) pairs, [3..5] the queue tails, [6] edge
+// entries read, [8 + i] the vertices source i reached at this level; all
+// added to, zeroed by the caller between levels.
+struct lux_msbfs_args {
+  const lux::E_ID* in_ptr;        // u64[nv+1]
+  const lux::V_ID* in_col;        // u32[ne]
+  const lux::E_ID* out_ptr;       // u64[nv+1]
+  const lux::V_ID* out_col;       // u32[ne]
+  unsigned long long* seen;       // u64[nv]
+  unsigned long long* front;      // u64[nv]
+  unsigned long long* next;       // u64[nv]
+  unsigned long long* dist_sum;   // u64[nv]
+  double* harmonic;               // f64[nv]
+  uint32_t* reach;                // u32[nv]
+  const lux::V_ID* thr_in;        // u32[n_thr_in]
+  const lux::V_ID* wav_in;        // u32[n_wav_in]
+  const uint32_t* hub_in;         // u32[2 * n_hub_in]
+  lux::V_ID* qthr;                // u32[nv]
+  lux::V_ID* qwav;                // u32[nv]
+  uint32_t* qhub;                 // u32[2 * hubcap_out]
+  unsigned long long* meta;       // u64[meta_words]
+  lux::V_ID nv;
+  uint32_t n_thr_in;
+  uint32_t n_wav_in;
+  uint32_t n_hub_in;
+  uint32_t hubcap_out;
+  uint32_t hub;  // rows longer than this are cut into chunks of this many
+  uint32_t thr;  // min(hub, lux_gpu_msbfs_thread_limit())
+};
+uint32_t lux_gpu_msbfs_hub_default();
+uint32_t lux_gpu_msbfs_hub_max();
+uint32_t lux_gpu_msbfs_thread_limit();
+uint32_t lux_gpu_msbfs_pull_div_default();
+uint32_t lux_gpu_msbfs_meta_words();
+// Every entry returns -1 (and launches nothing) on bad arguments.
+int lux_gpu_msbfs_seed(uint64_t stream, const lux_msbfs_args* a,
+                       const lux::V_ID* sources, uint32_t k);
+int lux_gpu_msbfs_pull(uint64_t stream, const lux_msbfs_args* a,
+                       unsigned long long active);
+int lux_gpu_msbfs_push(uint64_t stream, const lux_msbfs_args* a,
+                       uint32_t nthr, uint32_t nwav, uint32_t nhub);
+int lux_gpu_msbfs_epilogue(uint64_t stream, const lux_msbfs_args* a,
+                           uint32_t d, uint32_t k, int* depth);
+int lux_gpu_msbfs_check(uint64_t stream, const lux_msbfs_args* a,
+                        const unsigned long long* seen, const int* depth,
+                        const lux::V_ID* sources, uint32_t k,
+                        unsigned long long* bad);
+
 }  // extern "C"
