@@ -1209,3 +1209,76 @@ def msbfs_check(stream, a, seen, depth, sources, k, bad):
     _msbfs_rc("msbfs_check", lib().lux_gpu_msbfs_check(
         _u64(stream), ctypes.byref(a), dp(seen), dp(depth), dp(sources),
         _u32(k), dp(bad)), a)
+
+
+# ---- batched personalised PageRank (ppr.hip) ----
+
+class PprArgs(ctypes.Structure):
+    """lux_ppr_args: the CSC, the out-degrees, the role lists by in-degree,
+    the hub scratch and the teleport list of one batch."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "in_ptr", "in_col", "outdeg", "grp_in", "wav_in", "hub_in",
+        "hub_rows", "scratch", "tp_bits", "tp_vertex", "tp_col",
+        "tp_weight")] + \
+        [(n, ctypes.c_uint32) for n in (
+            "nv", "n_grp", "n_wav", "n_hub_in", "n_hub_rows", "n_tp", "hub",
+            "width")] + [("damping", ctypes.c_float)]
+
+
+PPR_WIDTHS = (16, 32, 64)
+PPR_BATCH = 64
+
+
+def ppr_group_limit():
+    """PPR_GROUP: the longest row one lane group takes."""
+    return _gcol_const("lux_gpu_ppr_group_limit")
+
+
+def ppr_hub_default():
+    """PPR_HUB: the longest wave-role row when LUX_PPR_HUB is unset."""
+    return _gcol_const("lux_gpu_ppr_hub_default")
+
+
+def ppr_hub_min():
+    return _gcol_const("lux_gpu_ppr_hub_min")
+
+
+def ppr_hub_max():
+    return _gcol_const("lux_gpu_ppr_hub_max")
+
+
+def ppr_args(tensors, nv, n_grp, n_wav, n_hub_in, n_hub_rows, n_tp, hub,
+             width, damping):
+    """tensors: the 12 device arrays in the struct's order."""
+    return PprArgs(*(t.data_ptr() for t in tensors), nv, n_grp, n_wav,
+                   n_hub_in, n_hub_rows, n_tp, hub, width, damping)
+
+
+def _ppr_rc(name, rc, a):
+    if rc < 0:
+        raise ValueError(f"{name}: rc={rc}, nv={a.nv}, hub={a.hub}, "
+                         f"width={a.width}, roles {a.n_grp}/{a.n_wav}/"
+                         f"{a.n_hub_rows}, damping={a.damping}")
+    return rc
+
+
+def ppr_seed(stream, a, y, col_x0):
+    _ppr_rc("ppr_seed", lib().lux_gpu_ppr_seed(
+        _u64(stream), ctypes.byref(a), dp(y), dp(col_x0)), a)
+
+
+def ppr_sweep(stream, a, y_old, y_new, residual):
+    """One iteration; returns the launches it took."""
+    return _ppr_rc("ppr_sweep", lib().lux_gpu_ppr_sweep(
+        _u64(stream), ctypes.byref(a), dp(y_old), dp(y_new), dp(residual)), a)
+
+
+def ppr_unscale(stream, a, y, out, ld, col0, k):
+    _ppr_rc("ppr_unscale", lib().lux_gpu_ppr_unscale(
+        _u64(stream), ctypes.byref(a), dp(y), dp(out), _u32(ld), _u32(col0),
+        _u32(k)), a)
+
+
+def ppr_check(stream, a, y_old, y_new, bad):
+    _ppr_rc("ppr_check", lib().lux_gpu_ppr_check(
+        _u64(stream), ctypes.byref(a), dp(y_old), dp(y_new), dp(bad)), a)

@@ -35,6 +35,9 @@ class AppArgs:
         #                        (degree | id)
         self.kcore = None  # kcore: also report the size of this K-core
         self.truss = None  # truss: also report the size of this K-truss
+        self.damping = 0.85  # ppr: probability of following an edge
+        self.tol = 0.0  # ppr: stop at the first residual <= tol (0 = off)
+        self.top = 5  # ppr: vertices printed per source
 
 
 def parse_input_args(argv):
@@ -78,6 +81,12 @@ def parse_input_args(argv):
             a.kcore = int(argv[i + 1]); i += 2
         elif f == "-truss":
             a.truss = int(argv[i + 1]); i += 2
+        elif f == "-damping":
+            a.damping = float(argv[i + 1]); i += 2
+        elif f == "-tol":
+            a.tol = float(argv[i + 1]); i += 2
+        elif f == "-top":
+            a.top = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

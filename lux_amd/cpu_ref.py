@@ -223,6 +223,37 @@ def multi_source_stats(g: Graph, sources, div=8, batch=64):
                 closeness=closeness, level_trace=trace)
 
 
+def personalised_pagerank(g: Graph, seeds, damping, iters, tol=0.0):
+    """(x f64[nv, K], iterations, residuals) of the recurrence in API.md:
+    column c restarts uniformly over seeds[c] (an int or a list of distinct
+    ints), x^0 = t, x' = (1 - d) t + d * sum over the entries u -> v of
+    x[u] / outdeg(u), d = damping rounded to fp32. Mass leaks at vertices
+    without out-edges. residuals[i] is max |x^(i+1) - x^i| over everything;
+    with tol > 0 the run ends after the first one <= tol. Plain numpy fp64,
+    one np.add.at over the entry list per iteration."""
+    d = float(np.float32(damping))
+    sets = [[int(s)] if isinstance(s, (int, np.integer)) else
+            [int(v) for v in s] for s in seeds]
+    src = g.src.astype(np.int64)
+    dst = np.repeat(np.arange(g.nv, dtype=np.int64),
+                    np.diff(np.concatenate(([0], g.col_end)).astype(np.int64)))
+    outdeg = np.bincount(src, minlength=g.nv).astype(np.float64)
+    t = np.zeros((g.nv, len(sets)), np.float64)
+    for c, s in enumerate(sets):
+        t[s, c] = 1.0 / len(s)
+    x, residuals = t.copy(), []
+    for _ in range(iters):
+        y = x / np.maximum(outdeg, 1.0)[:, None]
+        acc = np.zeros_like(x)
+        np.add.at(acc, dst, y[src])
+        new = (1.0 - d) * t + d * acc
+        residuals.append(float(np.abs(new - x).max()))
+        x = new
+        if tol > 0.0 and residuals[-1] <= tol:
+            break
+    return x, len(residuals), residuals
+
+
 def scc(g: Graph) -> np.ndarray:
     """label u32[nv] of the directed graph as loaded (row v of the CSC lists
     the sources u of the edges u -> v; parallel edges and self-loops change

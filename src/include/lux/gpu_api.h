@@ -759,4 +759,60 @@ int lux_gpu_msbfs_check(uint64_t stream, const lux_msbfs_args* a,
                         const lux::V_ID* sources, uint32_t k,
                         unsigned long long* bad);
 
+// ppr.hip (batched personalised PageRank, `width` = 16 / 32 / 64 columns per
+// vertex; single rank). The state is two f32 buffers [nv][width], vertex-major,
+// in the stored form y = x / outdeg (x where outdeg == 0); the entry points
+// take them as arguments because they swap every iteration. grp_in / wav_in:
+// the vertices of in-degree [0, group limit] and (group limit, hub]; hub_in:
+// the {vertex, chunk} items of the longer rows, hub_rows their {vertex, first
+// item, items} triples; scratch f32[n_hub_in][width] takes the items' partial
+// vectors. The teleport is the list (tp_vertex, tp_col, tp_weight) sorted by
+// vertex, weight = (1 - damping) / |seed set|, and tp_bits has bit v set iff
+// v occurs in it.
+struct lux_ppr_args {
+  const lux::E_ID* in_ptr;     // u64[nv+1]
+  const lux::V_ID* in_col;     // u32[ne]
+  const uint32_t* outdeg;      // u32[nv]
+  const lux::V_ID* grp_in;     // u32[n_grp]
+  const lux::V_ID* wav_in;     // u32[n_wav]
+  const uint32_t* hub_in;      // u32[2 * n_hub_in]
+  const uint32_t* hub_rows;    // u32[3 * n_hub_rows]
+  float* scratch;              // f32[n_hub_in * width]
+  const uint32_t* tp_bits;     // u32[(nv + 31) / 32]
+  const lux::V_ID* tp_vertex;  // u32[n_tp], ascending
+  const uint32_t* tp_col;      // u32[n_tp], < width
+  const float* tp_weight;      // f32[n_tp]
+  lux::V_ID nv;
+  uint32_t n_grp;
+  uint32_t n_wav;
+  uint32_t n_hub_in;
+  uint32_t n_hub_rows;
+  uint32_t n_tp;
+  uint32_t hub;    // rows longer than this are cut into chunks of this many
+  uint32_t width;  // 16, 32 or 64
+  float damping;
+};
+uint32_t lux_gpu_ppr_group_limit();
+uint32_t lux_gpu_ppr_hub_default();
+uint32_t lux_gpu_ppr_hub_min();
+uint32_t lux_gpu_ppr_hub_max();
+// Every entry returns -1 (and launches nothing) on bad arguments.
+// seed: y = x^0 in stored form, x^0[v][c] = col_x0[c] for the entries of the
+// teleport list and 0 elsewhere (every entry of y is written).
+int lux_gpu_ppr_seed(uint64_t stream, const lux_ppr_args* a, float* y,
+                     const float* col_x0);
+// sweep: one iteration y_old -> y_new; *residual (the bits of a non-negative
+// f32, raised with an integer atomic max) takes max |x_new - x_old|. Returns
+// the number of launches (1, or 2 with hub rows).
+int lux_gpu_ppr_sweep(uint64_t stream, const lux_ppr_args* a,
+                      const float* y_old, float* y_new, float* residual);
+// unscale: out[v * ld + col0 + c] = x[v][c] for c < k.
+int lux_gpu_ppr_unscale(uint64_t stream, const lux_ppr_args* a, const float* y,
+                        float* out, uint32_t ld, uint32_t col0, uint32_t k);
+// check: *bad += the entries of y_new further than (indeg + 6) * 2^-23
+// relative (1e-30 absolute) from one serial pass over the row of y_old.
+int lux_gpu_ppr_check(uint64_t stream, const lux_ppr_args* a,
+                      const float* y_old, const float* y_new,
+                      unsigned long long* bad);
+
 }  // extern "C"
