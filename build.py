@@ -42,6 +42,8 @@ HIPFLAGS_EXTRA = {
                   "-packed-fp32-ops"],
     "ppr.hip": ["-Xclang", "-target-feature", "-Xclang",
                 "-packed-fp32-ops"],
+    "cf_topn.hip": ["-Xclang", "-target-feature", "-Xclang",
+                    "-packed-fp32-ops"],
 }
 
 

@@ -1282,3 +1282,65 @@ def ppr_unscale(stream, a, y, out, ld, col0, k):
 def ppr_check(stream, a, y_old, y_new, bad):
     _ppr_rc("ppr_check", lib().lux_gpu_ppr_check(
         _u64(stream), ctypes.byref(a), dp(y_old), dp(y_new), dp(bad)), a)
+
+
+# ---- CF top-N recommendation (cf_topn.hip) ----
+
+class CfTopnArgs(ctypes.Structure):
+    """lux_cf_topn_args: the factors, the queries, the exclusion CSR, the
+    result and partial-list buffers and the work split of one call."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "vec", "queries", "excl_ptr", "excl_adj", "out_items", "out_scores",
+        "part_items", "part_scores")] + [("n_excl", ctypes.c_uint64)] + \
+        [(n, ctypes.c_uint32) for n in (
+            "nv", "K", "q", "n", "c_lo", "c_hi", "splits",
+            "tiles_per_split")]
+
+
+CF_TOPN_TILE = 64
+CF_TOPN_NMAX = 64
+CF_TOPN_KMAX = 128
+
+
+def cf_topn_plan(q, m, n, force=0):
+    """The number of splits of m candidates for q queries with lists of n
+    (force: 0 = the occupancy rule)."""
+    f = lib().lux_gpu_cf_topn_plan
+    f.restype = ctypes.c_uint32
+    return int(f(_u32(q), _u32(m), _u32(n), _u32(force)))
+
+
+def cf_topn_args(tensors, n_excl, nv, K, q, n, c_lo, c_hi, splits):
+    """tensors: the 8 device arrays in the struct's order (the last two may
+    be None with splits == 1)."""
+    tiles = (c_hi - c_lo + CF_TOPN_TILE - 1) // CF_TOPN_TILE
+    return CfTopnArgs(*(None if t is None else t.data_ptr() for t in tensors),
+                      n_excl, nv, K, q, n, c_lo, c_hi, splits,
+                      (tiles + splits - 1) // splits)
+
+
+def _cf_topn_rc(name, rc, a):
+    if rc < 0:
+        raise ValueError(f"{name}: rc={rc}, nv={a.nv}, K={a.K}, q={a.q}, "
+                         f"n={a.n}, candidates [{a.c_lo}, {a.c_hi}), splits="
+                         f"{a.splits} x {a.tiles_per_split} tiles")
+    return rc
+
+
+def cf_topn(stream, a):
+    """Scoring and selection (and the merge); returns the launches."""
+    return _cf_topn_rc("cf_topn", lib().lux_gpu_cf_topn(
+        _u64(stream), ctypes.byref(a)), a)
+
+
+def cf_topn_check(stream, a, items, scores, bad):
+    _cf_topn_rc("cf_topn_check", lib().lux_gpu_cf_topn_check(
+        _u64(stream), ctypes.byref(a), dp(items), dp(scores), dp(bad)), a)
+
+
+def cf_topn_keys(stream, nrows, row_ptr, col, e0, e1, out):
+    rc = lib().lux_gpu_cf_topn_keys(_u64(stream), _u32(nrows), dp(row_ptr),
+                                    dp(col), _u64(e0), _u64(e1), dp(out))
+    if rc < 0:
+        raise ValueError(f"cf_topn_keys: rc={rc}, nrows={nrows}, entries "
+                         f"[{e0}, {e1})")

@@ -45,7 +45,41 @@ def main(argv=None):
     with ElapsedTimer():
         for _ in range(a.num_iter):
             eng.step()
+    if a.topn:
+        recommend(a, part, eng)
     return eng
+
+
+def recommend(a, part, eng):
+    """-topn N [-queries Q]: the N best unseen items of users 0..Q-1 from
+    the trained factors, timed on its own."""
+    import time
+
+    import torch
+
+    from ..cf_topn_engine import CFTopN
+    if dx.world_size() > 1:
+        raise SystemExit("-topn is single-rank")
+    if part.n_users is None:
+        raise SystemExit("-topn needs the user/item boundary: -users N or a "
+                         "bipartite spec")
+    nq = min(a.queries, part.n_users) if a.queries > 0 else part.n_users
+    rec = CFTopN(part, eng.vectors())
+    users = torch.arange(nq, dtype=torch.int32, device=part.col.device)
+    rec.seen()  # the exclusion rows are built once, outside the timing
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    items, scores = rec.recommend(users, n=a.topn)
+    torch.cuda.synchronize()
+    print("TOPN TIME = %7.7f s (%d users x %d items, n = %d, %d splits)"
+          % (time.perf_counter() - t0, nq, part.nv - part.n_users, a.topn,
+             rec.stats["splits"]))
+    print(f"check() = {rec.check()}")
+    for u in range(min(nq, 3)):
+        row = ", ".join(f"{i}:{s:.4f}" for i, s in
+                        zip(items[u].tolist(), scores[u].tolist()))
+        print(f"user {u}: {row}")
+    return rec
 
 
 if __name__ == "__main__":

@@ -38,6 +38,9 @@ class AppArgs:
         self.damping = 0.85  # ppr: probability of following an edge
         self.tol = 0.0  # ppr: stop at the first residual <= tol (0 = off)
         self.top = 5  # ppr: vertices printed per source
+        self.topn = 0  # col_filter: recommend this many items per user after
+        #                the training loop (0 = off)
+        self.queries = 0  # col_filter -topn: users 0..Q-1 (0 = all users)
 
 
 def parse_input_args(argv):
@@ -87,6 +90,10 @@ def parse_input_args(argv):
             a.tol = float(argv[i + 1]); i += 2
         elif f == "-top":
             a.top = int(argv[i + 1]); i += 2
+        elif f == "-topn":
+            a.topn = int(argv[i + 1]); i += 2
+        elif f == "-queries":
+            a.queries = int(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

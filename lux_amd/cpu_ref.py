@@ -363,3 +363,27 @@ def cf_als(g: Graph, K: int, iters: int, lam: float = 0.001,
             _solve_rows(vec, vec, 0, n_users)
             _solve_rows(vec, vec, n_users, g.nv)
     return vec
+
+
+def cf_topn(vectors, queries, c_lo, c_hi, n, excl_ptr=None, excl_adj=None):
+    """Plain-numpy CF top-N (CFTopN's oracle; no C++ twin): for each query
+    the first n candidates of [c_lo, c_hi) outside row `query` of the
+    exclusion CSR, by descending float64 dot product and ascending id among
+    equal scores. -> (items i32[q, n], scores f64[q, n]), padded with -1 and
+    -inf."""
+    vec = np.asarray(vectors, dtype=np.float64)
+    queries = np.asarray(queries, dtype=np.int64)
+    cand = np.arange(c_lo, c_hi, dtype=np.int64)
+    items = np.full((queries.size, n), -1, np.int32)
+    scores = np.full((queries.size, n), -np.inf, np.float64)
+    for p, u in enumerate(queries):
+        ok = np.ones(cand.size, bool)
+        if excl_ptr is not None:
+            row = np.asarray(excl_adj[int(excl_ptr[u]):int(excl_ptr[u + 1])],
+                             dtype=np.int64)
+            ok = ~np.isin(cand, row)
+        s = vec[cand[ok]] @ vec[u]
+        best = np.lexsort((cand[ok], -s))[:n]
+        items[p, :best.size] = cand[ok][best]
+        scores[p, :best.size] = s[best]
+    return items, scores

@@ -815,4 +815,50 @@ int lux_gpu_ppr_check(uint64_t stream, const lux_ppr_args* a,
                       const float* y_old, const float* y_new,
                       unsigned long long* bad);
 
+// cf_topn.hip (CF top-N: for each of q query vertices the first n admissible
+// candidates of [c_lo, c_hi) by descending fp32 dot product, ties by
+// ascending id; single rank). Query u may not receive an item of row u of
+// the exclusion CSR (excl_ptr, excl_adj), whose rows are ascending (repeats
+// allowed) and are clamped to n_excl entries. A query id >= nv yields an
+// all-padding row (-1 / -inf). With splits > 1 the candidate tiles (64 items)
+// are cut into `splits` runs of tiles_per_split, the partial lists go to
+// part_* [splits][q][n] and a merge launch writes out_*.
+struct lux_cf_topn_args {
+  const float* vec;            // f32[nv][K]
+  const lux::V_ID* queries;    // u32[q]
+  const long long* excl_ptr;   // i64[nv+1]
+  const lux::V_ID* excl_adj;   // u32[n_excl]
+  int* out_items;              // i32[q][n]
+  float* out_scores;           // f32[q][n]
+  int* part_items;             // i32[splits][q][n], splits > 1 only
+  float* part_scores;          // f32[splits][q][n]
+  unsigned long long n_excl;
+  lux::V_ID nv;
+  uint32_t K;                  // 1..128
+  uint32_t q;
+  uint32_t n;                  // 1..64
+  lux::V_ID c_lo;
+  lux::V_ID c_hi;              // <= min(nv, 2^31 - 1)
+  uint32_t splits;
+  uint32_t tiles_per_split;
+};
+// plan: the number of splits for q queries over m candidates with lists of
+// n; `force` != 0 replaces the rule (twice the CU count of workgroups), the
+// caps at the tile count and at 2048 / n (the merge stages splits * n entries
+// in LDS) and "no empty split" still apply. 0 on bad arguments.
+uint32_t lux_gpu_cf_topn_plan(uint32_t q, uint32_t m, uint32_t n,
+                              uint32_t force);
+// Every entry returns -1 (and launches nothing) on bad arguments.
+// topn: returns the number of launches (1, or 2 with splits > 1).
+int lux_gpu_cf_topn(uint64_t stream, const lux_cf_topn_args* a);
+// check: bad[p] = the violations of row p of (items, scores) found by one
+// serial fmaf pass per candidate (see API.md); necessary, not sufficient.
+int lux_gpu_cf_topn_check(uint64_t stream, const lux_cf_topn_args* a,
+                          const int* items, const float* scores,
+                          uint32_t* bad);
+// keys: out[e - e0] = (row << 32) | col[e] for the CSC entries [e0, e1).
+int lux_gpu_cf_topn_keys(uint64_t stream, uint32_t nrows,
+                         const lux::E_ID* row_ptr, const lux::V_ID* col,
+                         uint64_t e0, uint64_t e1, unsigned long long* out);
+
 }  // extern "C"
