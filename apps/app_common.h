@@ -35,6 +35,8 @@ struct AppArgs {
                                // (auto-set from -synthetic bipartite:...)
   bool weighted = false;       // sssp: min-plus over edge weights — Python
                                // engine only; the native driver refuses
+  bool implicit_als = false;   // col_filter: implicit-feedback ALS — Python
+                               // engine only; the native driver refuses
 };
 
 inline AppArgs parse_input_args(int argc, char** argv) {
@@ -55,6 +57,7 @@ inline AppArgs parse_input_args(int argc, char** argv) {
     else if (f == "-users") a.users = (lux::V_ID)atoll(next());
     else if (f == "-labelprop") a.labelprop = true;
     else if (f == "-weighted") a.weighted = true;
+    else if (f == "-implicit") a.implicit_als = true;
     else if (f == "-wmax") next();  // value of the Python driver's flag
     else if (f.rfind("-ll:", 0) == 0 || f.rfind("-lg:", 0) == 0) {
       if (i + 1 < argc && argv[i + 1][0] != '-') i++;  // value-flag: skip

@@ -12,6 +12,15 @@ using namespace lux;
 
 int main(int argc, char** argv) {
   AppArgs a = parse_input_args(argc, argv);
+  if (a.implicit_als) {
+    // the native runtime has the SGD and explicit ALS sweeps only; running
+    // one of them for an -implicit request would be silently wrong
+    fprintf(stderr,
+            "col_filter: -implicit is not supported by the native runtime; "
+            "run `python -m lux_amd.apps.cf -als -implicit ...` for "
+            "implicit-feedback ALS\n");
+    return 2;
+  }
   if (const char* mr = getenv("LUX_MULTI_RANK")) {
     // re-exec'd native multi-GPU worker (SGD or MFMA ALS sweeps)
     HostCSC g;

@@ -44,6 +44,8 @@ HIPFLAGS_EXTRA = {
                 "-packed-fp32-ops"],
     "cf_topn.hip": ["-Xclang", "-target-feature", "-Xclang",
                     "-packed-fp32-ops"],
+    "cf_ials.hip": ["-Xclang", "-target-feature", "-Xclang",
+                    "-packed-fp32-ops"],
 }
 
 

@@ -423,6 +423,45 @@ def cf_als_iter(stream, n0, bin0, n1, bin1, n2, bin2, nbig, bin2v, hubidx,
         dp(newv), _u32(row_left), ctypes.c_int(K))
 
 
+def cf_ials_gram_scratch_floats(n):
+    """Floats of side-Gram scratch for a side of n rows."""
+    f = lib().lux_gpu_cf_ials_gram_wgs
+    f.restype = ctypes.c_uint32
+    g = lib().lux_gpu_cf_ials_gram_wg_floats
+    g.restype = ctypes.c_uint32
+    return f(_u32(n)) * g()
+
+
+def cf_ials_slot_floats():
+    f = lib().lux_gpu_cf_ials_slot_floats
+    f.restype = ctypes.c_uint32
+    return f()
+
+
+def cf_ials_side_gram(stream, table, lo, hi, K, scratch, out):
+    rc = lib().lux_gpu_cf_ials_side_gram(_u64(stream), dp(table), _u32(lo),
+                                         _u32(hi), ctypes.c_int(K),
+                                         dp(scratch), dp(out))
+    if rc < 0:
+        raise ValueError(f"cf_ials_side_gram: bad arguments (rows [{lo}, "
+                         f"{hi}), K={K})")
+    return rc
+
+
+def cf_ials_phase(stream, n0, bin0, n1, bin1, n2, chunks, nbig, hubs,
+                  hub_first, slots, row_ptr, col, w, oldv, newv, K, side_gram,
+                  alpha, reg):
+    rc = lib().lux_gpu_cf_ials_phase(
+        _u64(stream), _u32(n0), dp(bin0), _u32(n1), dp(bin1), _u32(n2),
+        dp(chunks), _u32(nbig), dp(hubs), dp(hub_first), dp(slots),
+        dp(row_ptr), dp(col), dp(w), dp(oldv), dp(newv), ctypes.c_int(K),
+        dp(side_gram), ctypes.c_float(alpha), ctypes.c_float(reg))
+    if rc < 0:
+        raise ValueError(f"cf_ials_phase: bad arguments (K={K}, alpha="
+                         f"{alpha}, reg={reg}, nbig={nbig}, n2={n2})")
+    return rc
+
+
 def frontier_expand(stream, old_dense, in_row_left, in_count, old_seg,
                     qlabels, labels_repair, push_row_ptr, items, counter,
                     max_items):

@@ -1,5 +1,7 @@
 """Collaborative filtering app driver (reference parity:
-col_filter/colfilter.cc; SGD matrix-factorization sweeps, rank -k)."""
+col_filter/colfilter.cc; SGD matrix-factorization sweeps, rank -k).
+-als selects the exact ALS optimizer, -als -implicit [-alpha A] [-reg L] the
+implicit-feedback ALS (CFImplicitALSEngine)."""
 import sys
 
 from .. import dist as dx
@@ -30,6 +32,10 @@ def build_cf_bench(args, device):
 
 def main(argv=None):
     a = parse_input_args(sys.argv[1:] if argv is None else argv)
+    if a.implicit and not a.als:
+        raise SystemExit("-implicit is an ALS variant: add -als")
+    if a.implicit and not 1 <= a.k <= 64:
+        raise SystemExit("-implicit covers -k 1..64")
     dx.init_process_group("cuda")
     import torch
     local = dx.env_local_rank()
@@ -41,10 +47,28 @@ def main(argv=None):
     if dx.rank() == 0:
         print_memory_estimate(part.nv, part.ne, dx.world_size(),
                               weighted=True, k=a.k)
-    eng = (CFALSEngine if a.als else CFEngine)(part, K=a.k)
+    if a.implicit:
+        from ..cf_ials_engine import CFImplicitALSEngine
+        if part.n_users is None:
+            raise SystemExit("-implicit needs the user/item boundary: "
+                             "-users N or a bipartite spec")
+        try:
+            eng = CFImplicitALSEngine(part, K=a.k, alpha=a.alpha, reg=a.reg)
+        except ValueError as e:
+            raise SystemExit(f"-implicit: {e}")
+    else:
+        eng = (CFALSEngine if a.als else CFEngine)(part, K=a.k)
     with ElapsedTimer():
         for _ in range(a.num_iter):
             eng.step()
+    if a.implicit and a.num_iter > 0 and dx.rank() == 0:
+        ms = eng.phase_ms
+        print("[lux] implicit ALS: alpha = %g, reg = %g; last sweep: side "
+              "Gram %.3f ms, row solves %.3f ms, hub rows %.3f ms; %d hub "
+              "rows, %d chunk slots, %d scratch bytes"
+              % (a.alpha, a.reg, ms["side_gram"], ms["solve"], ms["hub"],
+                 eng.stats["hub_rows"], eng.stats["chunk_slots"],
+                 eng.stats["scratch_bytes"]))
     if a.topn:
         recommend(a, part, eng)
     return eng

@@ -41,6 +41,9 @@ class AppArgs:
         self.topn = 0  # col_filter: recommend this many items per user after
         #                the training loop (0 = off)
         self.queries = 0  # col_filter -topn: users 0..Q-1 (0 = all users)
+        self.implicit = False  # col_filter -als: implicit-feedback ALS
+        self.alpha = 40.0  # col_filter -implicit: confidence 1 + alpha * w
+        self.reg = 0.01  # col_filter -implicit: regulariser
 
 
 def parse_input_args(argv):
@@ -94,6 +97,12 @@ def parse_input_args(argv):
             a.topn = int(argv[i + 1]); i += 2
         elif f == "-queries":
             a.queries = int(argv[i + 1]); i += 2
+        elif f == "-implicit":
+            a.implicit = True; i += 1
+        elif f == "-alpha":
+            a.alpha = float(argv[i + 1]); i += 2
+        elif f == "-reg":
+            a.reg = float(argv[i + 1]); i += 2
         elif f.startswith("-ll:") or f.startswith("-lg:"):
             # Legion runtime flags: accepted for CLI compatibility
             i += 2 if i + 1 < len(argv) and not argv[i + 1].startswith("-") \

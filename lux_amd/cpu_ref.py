@@ -365,6 +365,60 @@ def cf_als(g: Graph, K: int, iters: int, lam: float = 0.001,
     return vec
 
 
+def cf_ials(g: Graph, K: int, iters: int, alpha: float, reg: float, init,
+            n_users: int) -> np.ndarray:
+    """Plain-numpy implicit-feedback ALS (CFImplicitALSEngine's oracle), all
+    float64. Per sweep the user rows [0, n_users) are solved against the item
+    factors, then the item rows against the UPDATED users. For row v with Y the
+    factor rows of the whole other side and (y_e, w_e) its CSC entries:
+        A = Y^T Y + alpha * sum_e w_e y_e y_e^T + reg I
+        b = sum_e (1 + alpha w_e) y_e,        x_v = A^-1 b
+    The sums run per ENTRY (a parallel edge is one more observation); a row
+    with no entries gets x_v = 0."""
+    vec = np.array(init, dtype=np.float64).reshape(g.nv, K).copy()
+    eye = reg * np.eye(K)
+
+    def _phase(lo, hi, olo, ohi):
+        Y = vec[olo:ohi]
+        base = Y.T @ Y + eye
+        b = 0 if lo == 0 else int(g.col_end[lo - 1])
+        for v in range(lo, hi):
+            e = int(g.col_end[v])
+            if e > b:
+                S = vec[g.src[b:e]]
+                w = g.weight[b:e].astype(np.float64)
+                A = base + alpha * (S.T * w) @ S
+                vec[v] = np.linalg.solve(A, (1.0 + alpha * w) @ S)
+            else:
+                vec[v] = 0.0
+            b = e
+
+    for _ in range(iters):
+        # in place is exact: a row only reads the other side's factors
+        _phase(0, n_users, n_users, g.nv)
+        _phase(n_users, g.nv, 0, n_users)
+    return vec
+
+
+def cf_ials_loss(g: Graph, K: int, vec, alpha: float, reg: float,
+                 n_users: int) -> float:
+    """The objective both cf_ials phases minimise exactly when every rating
+    is stored both ways, dense in float64 (users x items table):
+        sum_{u,i} (x_u.y_i)^2
+        + sum_e [alpha w_e (x.y)^2 - 2 (1 + alpha w_e) (x.y)]
+        + reg (|X|^2 + |Y|^2),    e over the user-side entries."""
+    vec = np.asarray(vec, dtype=np.float64).reshape(g.nv, K)
+    X, Y = vec[:n_users], vec[n_users:]
+    ne_u = int(g.col_end[n_users - 1]) if n_users else 0
+    dst = np.repeat(np.arange(g.nv), np.diff(g.col_end.astype(np.int64),
+                                             prepend=0))[:ne_u]
+    p = np.einsum("ek,ek->e", vec[dst], vec[g.src[:ne_u]])
+    w = g.weight[:ne_u].astype(np.float64)
+    return float(((X @ Y.T) ** 2).sum()
+                 + (alpha * w * p * p - 2.0 * (1.0 + alpha * w) * p).sum()
+                 + reg * ((X * X).sum() + (Y * Y).sum()))
+
+
 def cf_topn(vectors, queries, c_lo, c_hi, n, excl_ptr=None, excl_adj=None):
     """Plain-numpy CF top-N (CFTopN's oracle; no C++ twin): for each query
     the first n candidates of [c_lo, c_hi) outside row `query` of the

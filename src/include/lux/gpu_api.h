@@ -337,6 +337,35 @@ void lux_gpu_cf_als_iter(uint64_t stream, uint32_t n0, const lux::V_ID* bin0,
                          const uint16_t* oldv_bf /*nullable*/, float* newv,
                          lux::V_ID row_left, int K);
 
+// cf_ials.hip (implicit-feedback ALS, fp32, 1 <= K <= 64; see API.md)
+// side_gram: out = f32[64 * 64], Y^T Y over rows [lo, hi) of `table`
+// (f32[nv][K]); rows and columns >= K are zero, no regulariser. scratch holds
+// gram_wgs(hi - lo) * gram_wg_floats() floats and needs no clearing. No
+// atomics: the same input gives the same bits. Returns the number of launches,
+// -1 (nothing launched) on bad arguments.
+uint32_t lux_gpu_cf_ials_gram_wgs(uint32_t n);
+uint32_t lux_gpu_cf_ials_gram_wg_floats(void);
+int lux_gpu_cf_ials_side_gram(uint64_t stream, const float* table,
+                              lux::V_ID lo, lux::V_ID hi, int K,
+                              float* scratch, float* out);
+// phase: solves the rows of bin0 / bin1 (deg < 2048, one wave each) and the
+// nbig rows of `hubs`, x_v = (side_gram + alpha sum_e w_e y_e y_e^T +
+// reg I)^-1 sum_e (1 + alpha w_e) y_e, into newv. Rows in no list are not
+// written. chunks = uint2[n2] {row, chunk}, sorted by (row, chunk): the
+// 8192-entry chunks of the hub rows; hub i owns entries and scratch slots
+// [hub_first[i], hub_first[i + 1]) (hub_first = u32[nbig + 1]); slots holds
+// n2 * slot_floats() floats and needs no clearing. Returns the number of
+// launches, -1 on bad arguments.
+uint32_t lux_gpu_cf_ials_slot_floats(void);
+int lux_gpu_cf_ials_phase(uint64_t stream, uint32_t n0, const lux::V_ID* bin0,
+                          uint32_t n1, const lux::V_ID* bin1, uint32_t n2,
+                          const lux_uint2* chunks, uint32_t nbig,
+                          const lux::V_ID* hubs, const uint32_t* hub_first,
+                          float* slots, const lux::E_ID* row_ptr,
+                          const lux::V_ID* col, const lux::WeightType* w,
+                          const float* oldv, float* newv, int K,
+                          const float* side_gram, float alpha, float reg);
+
 // bc.hip (betweenness centrality, single rank)
 // Records: lux_uint2[nv] {depth, value}. Level order: a counting sort of the
 // reached rows by key = depth*3 + degree bin into a u32 word list (a row id
