@@ -38,6 +38,8 @@ HIPFLAGS_EXTRA = {
                   "-packed-fp32-ops"],
     "lpa.hip": ["-Xclang", "-target-feature", "-Xclang",
                 "-packed-fp32-ops"],
+    "louvain.hip": ["-Xclang", "-target-feature", "-Xclang",
+                    "-packed-fp32-ops"],
     "msbfs.hip": ["-Xclang", "-target-feature", "-Xclang",
                   "-packed-fp32-ops"],
     "ppr.hip": ["-Xclang", "-target-feature", "-Xclang",

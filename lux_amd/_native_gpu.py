@@ -1166,6 +1166,90 @@ def lpa_stats(stream, nv, aptr, aadj, label, sizes, tot, intra):
                             dp(label), dp(sizes), dp(tot), dp(intra))
 
 
+# ---- community detection by modularity optimisation (louvain.hip) ----
+
+class LouvainArgs(ctypes.Structure):
+    """lux_louvain_args: one level graph, its class order and hub items, and
+    the state of its sweeps."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "aptr", "aadj", "aw", "k", "selfw", "vorder", "cptr", "comm", "tot",
+        "next", "hubv", "hubp", "hubr", "hptr", "hubbest", "hubdone",
+        "meta")] + [("W", ctypes.c_uint64)] + \
+        [(n, ctypes.c_uint32) for n in (
+            "nv", "ncls", "nitems", "nhub", "hub", "table")]
+
+
+# meta words
+LOUVAIN_M_MOVED, LOUVAIN_M_IN, LOUVAIN_M_SQ, LOUVAIN_M_BAD = range(4)
+
+
+def louvain_const(name):
+    """hub_default, table_default, table_min, table_max, fuse_default,
+    fuse_max or meta_words of louvain.hip."""
+    return _gcol_const(f"lux_gpu_louvain_{name}")
+
+
+def louvain_row_limit(hub, table):
+    """The longest row the table role takes at these knobs (as
+    lpa_row_limit)."""
+    f = lib().lux_gpu_louvain_row_limit
+    f.restype = ctypes.c_uint32
+    return int(f(_u32(hub), _u32(table)))
+
+
+def louvain_args(aptr, aadj, aw, k, selfw, vorder, cptr, comm, tot, nxt,
+                 hubv, hubp, hubr, hptr, hubbest, hubdone, meta, W, nv, ncls,
+                 nitems, nhub, hub, table):
+    return LouvainArgs(*(t.data_ptr() for t in (
+        aptr, aadj, aw, k, selfw, vorder, cptr, comm, tot, nxt, hubv, hubp,
+        hubr, hptr, hubbest, hubdone, meta)), W, nv, ncls, nitems, nhub, hub,
+        table)
+
+
+def _louvain_rc(what, rc, a):
+    if rc != 0:
+        raise ValueError(f"{what}: rc={rc}, nv={a.nv}, W={a.W}, "
+                         f"hub={a.hub}, table={a.table}")
+
+
+def louvain_classes(stream, a, c0, c1, nrows, nitems, maxdeg, fused):
+    """Decide and apply classes [c0, c1): nrows entries of vorder, the
+    longest row maxdeg, nitems hub items; fused: one workgroup, class after
+    class."""
+    rc = lib().lux_gpu_louvain_classes(
+        _u64(stream), ctypes.byref(a), _u32(c0), _u32(c1), _u32(nrows),
+        _u32(nitems), _u32(maxdeg), ctypes.c_int(int(fused)))
+    _louvain_rc(f"louvain_classes [{c0}, {c1}), {nrows} rows, {nitems} "
+                f"items, fused={fused}", rc, a)
+
+
+def louvain_check(stream, a):
+    _louvain_rc("louvain_check",
+                lib().lux_gpu_louvain_check(_u64(stream), ctypes.byref(a)), a)
+
+
+def louvain_stats(stream, a):
+    _louvain_rc("louvain_stats",
+                lib().lux_gpu_louvain_stats(_u64(stream), ctypes.byref(a)), a)
+
+
+def louvain_relabel(stream, a, dense, n2, keys, wrec, self2):
+    _louvain_rc("louvain_relabel", lib().lux_gpu_louvain_relabel(
+        _u64(stream), ctypes.byref(a), dp(dense), _u32(n2), dp(keys),
+        dp(wrec), dp(self2)), a)
+
+
+def louvain_heads(stream, nrec, keys, n2, head, deg2):
+    lib().lux_gpu_louvain_heads(_u64(stream), _u64(nrec), dp(keys), _u32(n2),
+                                dp(head), dp(deg2))
+
+
+def louvain_reduce(stream, nrec, keys, wrec, pos, nent, n2, aadj2, aw2, k2):
+    lib().lux_gpu_louvain_reduce(_u64(stream), _u64(nrec), dp(keys),
+                                 dp(wrec), dp(pos), _u64(nent), _u32(n2),
+                                 dp(aadj2), dp(aw2), dp(k2))
+
+
 # ---- bit-parallel multi-source BFS (msbfs.hip) ----
 
 class MsbfsArgs(ctypes.Structure):

@@ -175,6 +175,129 @@ def community_stats(g: Graph, labels):
                 intra=intra, modularity=modularity(intra, m, tot[tot > 0]))
 
 
+def louvain(g: Graph, order="degree", seed=1, weighted=False, init=None,
+            max_sweeps=0, max_levels=0):
+    """(labels i32[nv], level_trace, sweep_trace) of the Louvain method as
+    API.md defines it (LouvainEngine's oracle): per level a greedy colouring,
+    sweeps over the colour classes (every member decides on the community
+    totals as they stand when its class starts, then the movers are applied),
+    the exact integer Qnum = W * in - sum tot^2 after every sweep, and a
+    contraction by a sort of the relabelled edge list. level_trace:
+    [(level, n, sweeps, moved, Qnum)], sweep_trace: [(level, sweep, moved,
+    Qnum)]. Plain numpy and Python ints, one sequential loop per class; no
+    roles, no tables, no adjacency records."""
+    nv = g.nv
+    dst = np.repeat(np.arange(nv, dtype=np.int64),
+                    np.diff(np.concatenate(([0], g.col_end)).astype(np.int64)))
+    src = g.src.astype(np.int64)
+    keep = src != dst
+    key = np.minimum(src, dst)[keep] * max(nv, 1) + \
+        np.maximum(src, dst)[keep]
+    ukey, inv = np.unique(key, return_inverse=True)
+    lo, hi = ukey // max(nv, 1), ukey % max(nv, 1)
+    w = np.ones(ukey.size, np.int64)
+    if weighted:
+        if g.weight is None:
+            raise ValueError("weighted=True needs g.weight")
+        if g.ne and int(g.weight.min()) < 1:
+            raise ValueError("every weight must be >= 1")
+        w = np.zeros(ukey.size, np.int64)
+        np.add.at(w, inv.reshape(-1), g.weight.astype(np.int64)[keep])
+    W = 2 * int(w.sum())
+    if W >= 1 << 32:
+        raise ValueError(f"W = {W} does not fit 32 bits")
+    if init is not None:
+        init = np.asarray(init)
+        if init.shape != (nv,) or init.dtype.kind not in "iu" or \
+                (nv and not 0 <= int(init.min()) <= int(init.max()) < nv):
+            raise ValueError(f"init must hold {nv} labels in [0, {nv})")
+    n, selfw = nv, np.zeros(nv, np.int64)
+    vmap = np.arange(nv, dtype=np.int64)
+    level_trace, sweep_trace = [], []
+    while True:
+        level = len(level_trace)
+        rows = np.concatenate([lo, hi])
+        o = np.argsort(rows, kind="stable")
+        adj, aw = np.concatenate([hi, lo])[o], np.concatenate([w, w])[o]
+        ptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=n))))
+        k = selfw.copy()
+        np.add.at(k, rows, np.concatenate([w, w]))
+        comm = np.arange(n, dtype=np.int64) if level or init is None else \
+            init.astype(np.int64)
+        tot = np.zeros(n, np.int64)
+        np.add.at(tot, comm, k)
+        tot, kk = tot.tolist(), k.tolist()
+        colour = greedy_colouring(Graph.from_edges(n, lo, hi), order, seed) \
+            if lo.size else np.zeros(n, np.int32)
+        seq = np.lexsort((np.arange(n), colour))
+        cuts = np.flatnonzero(np.diff(colour[seq])) + 1
+        classes = [c[ptr[c + 1] > ptr[c]].tolist()
+                   for c in np.split(seq, cuts)]
+
+        def qnum():
+            inside = int(selfw.sum()) + 2 * int(w[comm[lo] == comm[hi]].sum())
+            return W * inside - sum(t * t for t in tot)
+
+        best_q, sweeps, moved = qnum(), 0, 0
+        while True:
+            saved = comm.copy(), list(tot)
+            movers = 0
+            for cls in classes:
+                moves = []
+                for v in cls:
+                    A, kv = int(comm[v]), kk[v]
+                    cs, a = np.unique(comm[adj[ptr[v]:ptr[v + 1]]],
+                                      return_inverse=True)
+                    a = np.bincount(a.reshape(-1),
+                                    weights=aw[ptr[v]:ptr[v + 1]])
+                    own, best = -kv * (tot[A] - kv), None
+                    for c, ac in zip(cs.tolist(), a.astype(np.int64).tolist()):
+                        if c == A:
+                            own += ac * W
+                        else:
+                            s = ac * W - kv * tot[c]
+                            if best is None or s > best[0]:
+                                best = (s, c)  # cs ascends: the smallest c
+                    if best is not None and best[0] > own:
+                        moves.append((v, A, best[1]))
+                for v, A, c in moves:
+                    comm[v] = c
+                    tot[A] -= kk[v]
+                    tot[c] += kk[v]
+                movers += len(moves)
+            sweeps += 1
+            q = qnum()
+            sweep_trace.append((level, sweeps, movers, q))
+            if movers == 0:
+                break
+            if q <= best_q:
+                comm, tot = saved
+                break
+            best_q, moved = q, moved + movers
+            if max_sweeps > 0 and sweeps >= max_sweeps:
+                break
+        level_trace.append((level, n, sweeps, moved, best_q))
+        if moved == 0 and (level or init is None):
+            break  # an init is contracted even if nothing moved
+        used = np.unique(comm)
+        dense = np.searchsorted(used, comm)
+        vmap = dense[vmap]
+        selfw = np.bincount(dense, weights=selfw,
+                            minlength=used.size).astype(np.int64)
+        cl, ch = dense[lo], dense[hi]
+        np.add.at(selfw, cl[cl == ch], 2 * w[cl == ch])
+        n = int(used.size)
+        out = cl != ch
+        ukey, inv = np.unique(np.minimum(cl, ch)[out] * n +
+                              np.maximum(cl, ch)[out], return_inverse=True)
+        w2 = np.zeros(ukey.size, np.int64)
+        np.add.at(w2, inv.reshape(-1), w[out])
+        lo, hi, w = ukey // n, ukey % n, w2
+        if max_levels > 0 and len(level_trace) >= max_levels:
+            break
+    return vmap.astype(np.int32), level_trace, sweep_trace
+
+
 def multi_source_bfs(g: Graph, sources) -> np.ndarray:
     """i32[k, nv]: the hop distance from each source along the edges
     u -> v of the directed graph as loaded, -1 where unreached. One call of

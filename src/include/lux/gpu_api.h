@@ -732,6 +732,66 @@ void lux_gpu_lpa_stats(uint64_t stream, lux::V_ID nv, const lux::E_ID* aptr,
                        unsigned long long* sizes, unsigned long long* tot,
                        unsigned long long* intra);
 
+// louvain.hip (community detection by modularity optimisation, one colour
+// class at a time; single rank). One record describes one level graph: aptr /
+// aadj / aw its symmetric weighted adjacency, selfw and k per vertex, W the
+// sum of k (< 2^32). vorder / cptr and the hub items {hubv, hubp, hubr} /
+// hptr are as for lpa.hip. comm / tot: the community per vertex and the sum
+// of k per community id; next: the decisions of the class in flight.
+// hubbest: three words per hub item {score lo, score hi, community}; hubdone:
+// one word per hub row, zero between launches. meta u64[meta_words]: [0]
+// movers, [1] in, [2] sum tot^2, [3] rows the check mode would move; all
+// added to.
+struct lux_louvain_args {
+  const lux::E_ID* aptr;        // u64[nv+1]
+  const lux::V_ID* aadj;        // u32[entries]
+  const uint32_t* aw;           // u32[entries]
+  const uint32_t* k;            // u32[nv]
+  const uint32_t* selfw;        // u32[nv]
+  const lux::V_ID* vorder;      // u32[nv]
+  const uint32_t* cptr;         // u32[ncls+1]
+  uint32_t* comm;               // u32[nv]
+  unsigned long long* tot;      // u64[nv]
+  uint32_t* next;               // u32[nv]
+  const lux::V_ID* hubv;        // u32[nitems]
+  const uint32_t* hubp;         // u32[nitems]
+  const uint32_t* hubr;         // u32[nitems]
+  const uint32_t* hptr;         // u32[ncls+1]
+  unsigned long long* hubbest;  // u64[3 * nitems]
+  uint32_t* hubdone;            // u32[nhub]
+  unsigned long long* meta;     // u64[meta_words]
+  unsigned long long W;
+  lux::V_ID nv;
+  uint32_t ncls;
+  uint32_t nitems;
+  uint32_t nhub;
+  uint32_t hub;    // rows longer than this go through hub items
+  uint32_t table;  // slots of the LDS table, a power of two
+};
+uint32_t lux_gpu_louvain_hub_default();
+uint32_t lux_gpu_louvain_table_default();
+uint32_t lux_gpu_louvain_table_min();
+uint32_t lux_gpu_louvain_table_max();
+uint32_t lux_gpu_louvain_fuse_default();
+uint32_t lux_gpu_louvain_fuse_max();
+uint32_t lux_gpu_louvain_meta_words();
+uint32_t lux_gpu_louvain_row_limit(uint32_t hub, uint32_t table);
+int lux_gpu_louvain_classes(uint64_t stream, const lux_louvain_args* a,
+                            uint32_t c0, uint32_t c1, uint32_t nrows,
+                            uint32_t nitems, uint32_t maxdeg, int fused);
+int lux_gpu_louvain_check(uint64_t stream, const lux_louvain_args* a);
+int lux_gpu_louvain_stats(uint64_t stream, const lux_louvain_args* a);
+int lux_gpu_louvain_relabel(uint64_t stream, const lux_louvain_args* a,
+                            const uint32_t* dense, uint32_t n2,
+                            long long* keys, uint32_t* wrec, uint32_t* self2);
+void lux_gpu_louvain_heads(uint64_t stream, uint64_t nrec,
+                           const long long* keys, uint32_t n2,
+                           long long* head, uint32_t* deg2);
+void lux_gpu_louvain_reduce(uint64_t stream, uint64_t nrec,
+                            const long long* keys, const uint32_t* wrec,
+                            const long long* pos, uint64_t nent, uint32_t n2,
+                            lux::V_ID* aadj2, uint32_t* aw2, uint32_t* k2);
+
 // msbfs.hip (bit-parallel multi-source BFS, 64 sources per word; single
 // rank). in_ptr / in_col: the CSC, out_ptr / out_col: the out-edge CSR.
 // seen / front / next: one word per vertex, bit i = source i of the batch.
