@@ -48,6 +48,8 @@ HIPFLAGS_EXTRA = {
                     "-packed-fp32-ops"],
     "cf_ials.hip": ["-Xclang", "-target-feature", "-Xclang",
                     "-packed-fp32-ops"],
+    "clique.hip": ["-Xclang", "-target-feature", "-Xclang",
+                   "-packed-fp32-ops"],
 }
 
 

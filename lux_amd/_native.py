@@ -330,6 +330,15 @@ def tc_cpu(nv, ne, col_end, src):
     return int(total[0]), per_vertex
 
 
+def cliques_cpu(nv, ne, col_end, src, k):
+    total = np.zeros(1, np.uint64)
+    per_vertex = np.empty(nv, np.uint64)
+    cpu.lux_cliques_cpu(ctypes.c_uint32(nv), ctypes.c_uint64(ne),
+                        ptr(col_end, u64p), ptr(src, u32p), ctypes.c_int(k),
+                        ptr(total, u64p), ptr(per_vertex, u64p))
+    return int(total[0]), per_vertex
+
+
 def truss_cpu(nv, ne, col_end, src, want_truss=True):
     """(edges u32[m, 2] key-sorted, support u32[m], trussness u32[m] or
     None) of the underlying simple graph."""

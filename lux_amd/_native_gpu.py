@@ -612,6 +612,40 @@ def tc_count_plain(stream, nv, m, optr, oadj, counters, pv=None):
                                  dp(oadj), dp(counters), dp(pv))
 
 
+# ---- k-clique counting (clique.hip) ----
+
+def clique_const(name):
+    """cap_max, k_max or wave_max of clique.hip."""
+    f = getattr(lib(), f"lux_gpu_clique_{name}")
+    f.restype = ctypes.c_uint32
+    return int(f())
+
+
+def clique_count_items(stream, role, k, optr, oadj, items, nitems,
+                       cap_or_class, counters, pv=None):
+    """Count one role's items (role 0 wave, 1 block of one size class, 2 hub)
+    into counters (u64[4]: total, set_ops, spills, built_bits) and, with pv
+    (u64[nv], rank-indexed), the per-vertex counts."""
+    rc = lib().lux_gpu_clique_count_items(
+        _u64(stream), ctypes.c_int(role), ctypes.c_int(k), dp(optr),
+        dp(oadj), dp(items), _u32(nitems), _u32(cap_or_class), dp(counters),
+        dp(pv))
+    if rc == -2:
+        raise RuntimeError("clique_count_items: the dynamic-LDS limit could "
+                           "not be raised")
+    if rc != 0:
+        raise ValueError(f"clique_count_items: unsupported role={role} / "
+                         f"k={k} / cap={cap_or_class}")
+
+
+def clique_count_plain(stream, k, nv, m, optr, oadj, counters, pv=None):
+    rc = lib().lux_gpu_clique_count_plain(
+        _u64(stream), ctypes.c_int(k), _u32(nv), _u64(m), dp(optr), dp(oadj),
+        dp(counters), dp(pv))
+    if rc != 0:
+        raise ValueError(f"clique_count_plain: unsupported k={k}")
+
+
 # ---- k-core decomposition (kcore.hip) ----
 
 def _kcore_const(name):

@@ -33,6 +33,7 @@ class AppArgs:
         self.nsrc = 1  # bc: number of sources (-start, -start + 1, ...)
         self.order = "degree"  # tc: vertex order of the orientation
         #                        (degree | id)
+        self.clique = 4  # clique: the clique size K (3..8)
         self.kcore = None  # kcore: also report the size of this K-core
         self.truss = None  # truss: also report the size of this K-truss
         self.damping = 0.85  # ppr: probability of following an edge
@@ -83,6 +84,8 @@ def parse_input_args(argv):
             a.nsrc = int(argv[i + 1]); i += 2
         elif f == "-order":
             a.order = argv[i + 1]; i += 2
+        elif f == "-clique":
+            a.clique = int(argv[i + 1]); i += 2
         elif f == "-kcore":
             a.kcore = int(argv[i + 1]); i += 2
         elif f == "-truss":

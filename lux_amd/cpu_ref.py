@@ -85,6 +85,19 @@ def triangles(g: Graph):
     return nat.tc_cpu(g.nv, g.ne, g.col_end, g.src)
 
 
+def cliques(g: Graph, k: int):
+    """Exact k-clique counts, 3 <= k <= 8: (total int, per_vertex u64[nv])
+    on the simple undirected graph of triangles() (CliqueEngine's
+    definition). total counts the k-subsets of pairwise adjacent vertices,
+    per_vertex[v] those containing v: per_vertex.sum() == k * total. C++
+    recursive search on the id-oriented adjacency that narrows sorted
+    candidate lists with two-pointer merges; no bit sets, no degree order,
+    no code shared with tc_engine.orient."""
+    if not 3 <= k <= 8:
+        raise ValueError(f"k must be in 3..8, got {k}")
+    return nat.cliques_cpu(g.nv, g.ne, g.col_end, g.src, k)
+
+
 def edge_support(g: Graph):
     """(edges u32[m, 2], support u32[m]) on the simple undirected graph of
     triangles(): edges are (lo, hi) in original ids, sorted by the key

@@ -38,6 +38,8 @@ void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
             V_ID source, V_ID* depth, double* sigma, double* delta);
 void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
             uint64_t* total, uint64_t* per_vertex);
+void cliques_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+                 int k, uint64_t* total, uint64_t* per_vertex);
 E_ID truss_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
                V_ID* edges, uint32_t* support, uint32_t* trussness);
 void coreness_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
@@ -263,6 +265,11 @@ void lux_bc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
 void lux_tc_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
                 const uint32_t* src, uint64_t* total, uint64_t* per_vertex) {
   tc_cpu(nv, ne, col_end, src, total, per_vertex);
+}
+void lux_cliques_cpu(uint32_t nv, uint64_t ne, const uint64_t* col_end,
+                     const uint32_t* src, int k, uint64_t* total,
+                     uint64_t* per_vertex) {
+  cliques_cpu(nv, ne, col_end, src, k, total, per_vertex);
 }
 // edges u32[2 * ne], support u32[ne], trussness u32[ne] or null (support
 // only); returns the number of simple edges filled in.

@@ -318,8 +318,11 @@ void bc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
 // counting on the sorted, deduplicated, id-oriented (lo -> hi) adjacency:
 // for every arc u -> v, a merge of A(u) and A(v); each common w is the
 // triangle u < v < w, counted once in *total and once for each corner.
-void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
-            uint64_t* total, uint64_t* per_vertex) {
+// The sorted, deduplicated, id-oriented (lo -> hi) adjacency of the simple
+// graph: A(u) = adj[ptr[u] : ptr[u+1]), ascending, every entry > u.
+static void simple_oriented_adj(V_ID nv, E_ID ne, const E_ID* col_end,
+                                const V_ID* src, std::vector<E_ID>& ptr,
+                                std::vector<V_ID>& adj) {
   std::vector<uint64_t> keys;
   keys.reserve(ne);
   E_ID b = 0;
@@ -334,13 +337,20 @@ void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
   }
   std::sort(keys.begin(), keys.end());
   keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  std::vector<E_ID> ptr((size_t)nv + 1, 0);
-  std::vector<V_ID> adj(keys.size());
+  ptr.assign((size_t)nv + 1, 0);
+  adj.resize(keys.size());
   for (size_t k = 0; k < keys.size(); k++) {
     ptr[(keys[k] >> 32) + 1]++;
     adj[k] = (V_ID)(keys[k] & 0xFFFFFFFFu);
   }
   for (V_ID v = 0; v < nv; v++) ptr[v + 1] += ptr[v];
+}
+
+void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+            uint64_t* total, uint64_t* per_vertex) {
+  std::vector<E_ID> ptr;
+  std::vector<V_ID> adj;
+  simple_oriented_adj(nv, ne, col_end, src, ptr, adj);
   *total = 0;
   for (V_ID v = 0; v < nv; v++) per_vertex[v] = 0;
   for (V_ID u = 0; u < nv; u++) {
@@ -361,6 +371,73 @@ void tc_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
         }
       }
     }
+  }
+}
+
+// ---------- k-clique counting ----------
+// Exact oracle of CliqueEngine (no reference equivalent), on the same simple
+// undirected graph and id-oriented adjacency as tc_cpu. A k-clique
+// u < v1 < ... < v(k-1) is found once, from u: the candidates of the first
+// level are the list A(u); choosing v narrows them to the two-pointer merge
+// of the current list (past v) with A(v); the last level's list is the set
+// of completing vertices. Sorted lists only: no bit sets and no degree
+// order. k < 2 counts nothing.
+namespace {
+struct CliqueSearch {
+  const std::vector<E_ID>& ptr;
+  const std::vector<V_ID>& adj;
+  uint64_t* per_vertex;
+  std::vector<std::vector<V_ID>> lists;  // one candidate list per level
+
+  // cliques of `rem` more vertices inside lists[level]; every one adds 1 to
+  // each of its vertices chosen here, the caller adds the chosen above
+  uint64_t search(int level, int rem) {
+    const std::vector<V_ID>& cand = lists[level];
+    if (rem == 1) {
+      for (V_ID w : cand) per_vertex[w]++;
+      return cand.size();
+    }
+    uint64_t sum = 0;
+    for (size_t a = 0; a + 1 < cand.size(); a++) {
+      V_ID v = cand[a];
+      std::vector<V_ID>& next = lists[level + 1];
+      next.clear();
+      size_t i = a + 1;
+      E_ID j = ptr[v], je = ptr[v + 1];
+      while (i < cand.size() && j < je) {
+        if (cand[i] < adj[j]) i++;
+        else if (adj[j] < cand[i]) j++;
+        else {
+          next.push_back(cand[i]);
+          i++;
+          j++;
+        }
+      }
+      if (next.size() + 1 < (size_t)rem) continue;
+      uint64_t s = search(level + 1, rem - 1);
+      per_vertex[v] += s;
+      sum += s;
+    }
+    return sum;
+  }
+};
+}  // namespace
+
+void cliques_cpu(V_ID nv, E_ID ne, const E_ID* col_end, const V_ID* src,
+                 int k, uint64_t* total, uint64_t* per_vertex) {
+  std::vector<E_ID> ptr;
+  std::vector<V_ID> adj;
+  simple_oriented_adj(nv, ne, col_end, src, ptr, adj);
+  *total = 0;
+  for (V_ID v = 0; v < nv; v++) per_vertex[v] = 0;
+  if (k < 2) return;
+  CliqueSearch cs{ptr, adj, per_vertex,
+                  std::vector<std::vector<V_ID>>((size_t)k)};
+  for (V_ID u = 0; u < nv; u++) {
+    cs.lists[0].assign(adj.begin() + ptr[u], adj.begin() + ptr[u + 1]);
+    uint64_t s = cs.search(0, k - 1);
+    per_vertex[u] += s;
+    *total += s;
   }
 }
 

@@ -414,6 +414,34 @@ void lux_gpu_tc_count_plain(uint64_t stream, lux::V_ID nv, lux::E_ID m,
                             unsigned long long* counters,
                             unsigned long long* pv);
 
+// clique.hip (k-clique counting, 3 <= k <= k_max, single rank)
+// optr / oadj as for tc.hip. items: u32 pairs {u, p}, one list per role and
+// size class: 0 wave (a wave per row of k-1 .. wave_max arcs, the induced
+// DAG as 64 LDS words; cap_or_class is not read), 1 block (a workgroup per
+// row, the bit matrix in dynamic LDS; cap_or_class = the size class, every
+// listed row has at most that many arcs), 2 hub (p = an arc's offset in row
+// u; the matrix is built on A(u) & A(A(u)[p]); cap_or_class = the cap, an
+// arc with more common members is a spill and takes the listless search).
+// Classes and caps are multiples of 64 in 64..cap_max. counters: u64[4]
+// {total, set_ops, spills, built_bits}, added to. pv: u64[nv] rank-indexed
+// per-vertex counts, added to; null counts the total alone. count_items
+// returns -1 (nothing launched) on an unknown role, k or cap, -2 when the
+// dynamic-LDS limit cannot be raised; count_plain -1 on an unknown k.
+uint32_t lux_gpu_clique_cap_max();
+uint32_t lux_gpu_clique_k_max();
+uint32_t lux_gpu_clique_wave_max();
+int lux_gpu_clique_count_items(uint64_t stream, int role, int k,
+                               const lux::E_ID* optr, const lux::V_ID* oadj,
+                               const uint32_t* items, uint32_t nitems,
+                               uint32_t cap_or_class,
+                               unsigned long long* counters,
+                               unsigned long long* pv);
+int lux_gpu_clique_count_plain(uint64_t stream, int k, lux::V_ID nv,
+                               lux::E_ID m, const lux::E_ID* optr,
+                               const lux::V_ID* oadj,
+                               unsigned long long* counters,
+                               unsigned long long* pv);
+
 // kcore.hip (k-core decomposition by synchronous peeling, single rank)
 // optr u64[nv+1] / oadj u32[m]: the id-order DAG of the simple graph (row u
 // lists its neighbours > u). aptr u64[nv+1] / aadj u32[2m]: the full
