@@ -50,6 +50,8 @@ HIPFLAGS_EXTRA = {
                     "-packed-fp32-ops"],
     "clique.hip": ["-Xclang", "-target-feature", "-Xclang",
                    "-packed-fp32-ops"],
+    "bc_batch.hip": ["-Xclang", "-target-feature", "-Xclang",
+                     "-packed-fp32-ops"],
 }
 
 

@@ -1501,3 +1501,90 @@ def cf_topn_keys(stream, nrows, row_ptr, col, e0, e1, out):
     if rc < 0:
         raise ValueError(f"cf_topn_keys: rc={rc}, nrows={nrows}, entries "
                          f"[{e0}, {e1})")
+
+
+# ---- batched betweenness centrality (bc_batch.hip) ----
+
+class BcbLevel(ctypes.Structure):
+    """lux_bcb_level: one level of one pass of a batch."""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "list", "row_ptr", "adj", "dep", "val", "delta", "scratch",
+        "edges")] + \
+        [(n, ctypes.c_uint64) for n in (
+            "o0", "o1", "o2", "o3", "scratch_items")] + \
+        [(n, ctypes.c_uint32) for n in ("nv", "width", "hub", "d", "leaf")]
+
+
+BCB_WIDTHS = (16, 32, 64)
+
+
+def bcb_group_limit():
+    """BCB_GROUP: the longest row one lane group takes."""
+    return _gcol_const("lux_gpu_bcb_group_limit")
+
+
+def bcb_hub_default():
+    """BCB_HUB: the longest wave-role row when LUX_BCB_HUB is unset."""
+    return _gcol_const("lux_gpu_bcb_hub_default")
+
+
+def bcb_hub_min():
+    return _gcol_const("lux_gpu_bcb_hub_min")
+
+
+def bcb_hub_max():
+    return _gcol_const("lux_gpu_bcb_hub_max")
+
+
+def bcb_max_levels():
+    return _gcol_const("lux_gpu_bcb_max_levels")
+
+
+def _bcb_rc(name, rc, what):
+    if rc < 0:
+        raise ValueError(f"{name}: rc={rc}, {what}")
+    return rc
+
+
+def bcb_prepare(stream, nv, width, k, depth, dep, val, delta):
+    _bcb_rc("bcb_prepare", lib().lux_gpu_bcb_prepare(
+        _u64(stream), _u32(nv), _u32(width), _u32(k), dp(depth), dp(dep),
+        dp(val), dp(delta)), f"nv={nv}, width={width}, k={k}")
+
+
+def bcb_order_hist(stream, nv, width, dep, row_ptr, levels, hub, cnt,
+                   hubrows):
+    _bcb_rc("bcb_order_hist", lib().lux_gpu_bcb_order_hist(
+        _u64(stream), _u32(nv), _u32(width), dp(dep), dp(row_ptr),
+        _u32(levels), _u32(hub), dp(cnt), dp(hubrows)),
+        f"nv={nv}, width={width}, levels={levels}, hub={hub}")
+
+
+def bcb_order_scatter(stream, nv, width, dep, row_ptr, levels, hub, cursor,
+                      list_, cap):
+    _bcb_rc("bcb_order_scatter", lib().lux_gpu_bcb_order_scatter(
+        _u64(stream), _u32(nv), _u32(width), dp(dep), dp(row_ptr),
+        _u32(levels), _u32(hub), dp(cursor), dp(list_), _u64(cap)),
+        f"nv={nv}, width={width}, levels={levels}, hub={hub}, cap={cap}")
+
+
+def bcb_level(stream, a, forward):
+    """One level of one pass; returns the launches it took."""
+    return _bcb_rc("bcb_level", lib().lux_gpu_bcb_level(
+        _u64(stream), ctypes.byref(a), ctypes.c_int(int(bool(forward)))),
+        f"nv={a.nv}, width={a.width}, hub={a.hub}, level {a.d}, offsets "
+        f"{a.o0}/{a.o1}/{a.o2}/{a.o3}, scratch items {a.scratch_items}")
+
+
+def bcb_reduce(stream, nv, width, delta, bc):
+    _bcb_rc("bcb_reduce", lib().lux_gpu_bcb_reduce(
+        _u64(stream), _u32(nv), _u32(width), dp(delta), dp(bc)),
+        f"nv={nv}, width={width}")
+
+
+def bcb_check(stream, nv, width, in_ptr, in_adj, out_ptr, out_adj, dep,
+              sigma, delta, rtol, out):
+    _bcb_rc("bcb_check", lib().lux_gpu_bcb_check(
+        _u64(stream), _u32(nv), _u32(width), dp(in_ptr), dp(in_adj),
+        dp(out_ptr), dp(out_adj), dp(dep), dp(sigma), dp(delta),
+        ctypes.c_double(rtol), dp(out)), f"nv={nv}, width={width}")

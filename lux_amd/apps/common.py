@@ -31,6 +31,8 @@ class AppArgs:
         self.delta = 0  # sssp -weighted: bucket width of the bucketed
         #                 (near-far delta-stepping) schedule; 0 = off
         self.nsrc = 1  # bc: number of sources (-start, -start + 1, ...)
+        self.batch = 0  # bc: sources per sweep of the batched path (16 | 32
+        #                 | 64); 0 = one source at a time
         self.order = "degree"  # tc: vertex order of the orientation
         #                        (degree | id)
         self.clique = 4  # clique: the clique size K (3..8)
@@ -82,6 +84,10 @@ def parse_input_args(argv):
             a.delta = int(argv[i + 1]); i += 2
         elif f == "-nsrc":
             a.nsrc = int(argv[i + 1]); i += 2
+        elif f == "-batch":
+            a.batch = int(argv[i + 1]); i += 2
+            if a.batch not in (16, 32, 64):
+                raise SystemExit("-batch B needs B in {16, 32, 64}")
         elif f == "-order":
             a.order = argv[i + 1]; i += 2
         elif f == "-clique":
@@ -180,12 +186,13 @@ def attach_hash_weights(a, part):
     return part
 
 
-def print_memory_estimate(nv, ne, nparts, weighted=False, k=1):
+def print_memory_estimate(nv, ne, nparts, weighted=False, k=1, extra=0):
     """Startup FB-requirement printout, the analog of pagerank.cc:60-85 /
-    sssp.cc:59-90 against 288 GB HBM3E per MI355X."""
+    sssp.cc:59-90 against 288 GB HBM3E per MI355X. extra: bytes of state
+    the caller counts itself."""
     per_edge = 4 + (4 if weighted else 0)
     fb = ne * per_edge // max(nparts, 1) + 8 * (nv // max(nparts, 1) + 1) \
-        + 2 * 4 * k * nv
+        + 2 * 4 * k * nv + extra
     print(f"[lux] estimated FB usage per GPU: {fb / (1 << 20):.0f} MB "
           f"(of 294912 MB HBM3E)")
 

@@ -978,4 +978,68 @@ int lux_gpu_cf_topn_keys(uint64_t stream, uint32_t nrows,
                          const lux::E_ID* row_ptr, const lux::V_ID* col,
                          uint64_t e0, uint64_t e1, unsigned long long* out);
 
+// bc_batch.hip (batched betweenness centrality, `width` = 16 / 32 / 64
+// sources per sweep; single rank). State, vertex-major: dep u16[nv][width]
+// (0xFFFF unreached), val f32[nv][width] (sigma going forward, q = (1 +
+// delta) / sigma going backward), delta f32[nv][width]. A level list is u32
+// words ordered by key = depth * 3 + role (group, wave, hub): one word per
+// group- or wave-role entry, one {row, chunk} pair per `hub` edges of a hub
+// row; a row has one entry per distinct depth of its columns.
+struct lux_bcb_level {
+  const uint32_t* list;       // the direction's level list
+  const lux::E_ID* row_ptr;   // u64[nv+1]: CSC (forward) / out CSR (backward)
+  const lux::V_ID* adj;       // in-neighbours (forward) / out (backward)
+  const uint16_t* dep;
+  float* val;
+  float* delta;
+  float* scratch;             // f32[scratch_items][width], hub partials
+  unsigned long long* edges;  // += the (edge, column) pairs that passed
+  uint64_t o0, o1, o2, o3;    // word offsets: group, wave, hub, end
+  uint64_t scratch_items;
+  lux::V_ID nv;
+  uint32_t width;
+  uint32_t hub;               // edges per hub item
+  uint32_t d;                 // the level
+  uint32_t leaf;              // backward only: gather nothing, q = 1 / sigma
+};
+uint32_t lux_gpu_bcb_group_limit();
+uint32_t lux_gpu_bcb_hub_default();
+uint32_t lux_gpu_bcb_hub_min();
+uint32_t lux_gpu_bcb_hub_max();
+uint32_t lux_gpu_bcb_max_levels();
+// Every entry returns -1 (and launches nothing) on bad arguments.
+// prepare: depth is i32[k][nv], source-major, -1 unreached; writes every
+// entry of dep, val (1 at depth 0, else 0) and delta (0); columns >= k are
+// unreached.
+int lux_gpu_bcb_prepare(uint64_t stream, lux::V_ID nv, uint32_t width,
+                        uint32_t k, const int* depth, uint16_t* dep,
+                        float* val, float* delta);
+// cnt: zeroed u32[3 * levels], list words per key; hubrows: zeroed
+// u64[levels], hub-role entries per level.
+int lux_gpu_bcb_order_hist(uint64_t stream, lux::V_ID nv, uint32_t width,
+                           const uint16_t* dep, const lux::E_ID* row_ptr,
+                           uint32_t levels, uint32_t hub, uint32_t* cnt,
+                           unsigned long long* hubrows);
+// cursor: u64[3 * levels], each key's first word, consumed; list: u32[cap].
+int lux_gpu_bcb_order_scatter(uint64_t stream, lux::V_ID nv, uint32_t width,
+                              const uint16_t* dep, const lux::E_ID* row_ptr,
+                              uint32_t levels, uint32_t hub,
+                              unsigned long long* cursor, uint32_t* list,
+                              uint64_t cap);
+// level: one level of one pass; returns the launches (0, 1, or 2 with hub
+// items).
+int lux_gpu_bcb_level(uint64_t stream, const lux_bcb_level* a, int forward);
+// reduce: bc[v] += sum over the columns of delta[v][.], in a fixed order.
+int lux_gpu_bcb_reduce(uint64_t stream, lux::V_ID nv, uint32_t width,
+                       const float* delta, float* bc);
+// check: out (zeroed u64[2]) = {entries whose sigma or delta, recomputed in
+// fp64 from the final arrays, is off by more than rtol; reached entries with
+// a non-finite sigma}.
+int lux_gpu_bcb_check(uint64_t stream, lux::V_ID nv, uint32_t width,
+                      const lux::E_ID* in_ptr, const lux::V_ID* in_adj,
+                      const lux::E_ID* out_ptr, const lux::V_ID* out_adj,
+                      const uint16_t* dep, const float* sigma,
+                      const float* delta, double rtol,
+                      unsigned long long* out);
+
 }  // extern "C"
